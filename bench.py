@@ -25,9 +25,13 @@ pu_run_device_pool), so no slot idles.  `value` = all requests processed by
 all ranks / max-over-ranks wall time of the K timed steps.  Replay is open
 loop (recorded timers).
 
-At N=1 (rank 0) the same line also carries:
-  * per_simulation_accesses_per_s — value / wavefronts: the rate of ONE of the
-    concurrent simulations;
+A plain run does that and no more: it sets up, warms up, times the K steps,
+writes --dump-outputs if asked and prints the line (per_simulation_accesses_
+per_s — value / wavefronts, the rate of ONE of the concurrent simulations — and
+the roofline come from the timed steps' own counters).  Every other pass and
+check runs under --full and fills the fields that are null in a plain line.
+
+With --full, at N=1 (rank 0) the same line also carries:
   * replica_parity — the delays of 16 replicas spread over 0..R-1 (warmup and
     timed window) against the reference's, replayed by the ensemble processes;
   * single_instance — ONE simulation alone on the GPU (a 1-replica engine on
@@ -44,15 +48,28 @@ At N=1 (rank 0) the same line also carries:
   * roofline.traffic — fabric bytes (FETCH_SIZE + WRITE_SIZE, separate PMC
     passes; includes Infinity-Cache hits) measured by tools/pmc_traffic.py for
     THIS library build only (refused when its source hash differs).
-At N>1 every rank forks --rank-parity-workers reference processes before it
+With --full, at N>1 every rank forks --rank-parity-workers reference processes before it
 touches its GPU; they replay that rank's replica 0 and its first replica-pool
 spare, each rank checks their delays against its own, and rank 0's line
 carries `rank_parity` (per rank and overall) and `roofline.job` (algorithmic
 bytes summed over ranks / the slowest rank's mean launch / (N x 8 TB/s)).
 The run exits non-zero when a parity check fails on any rank.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; N>1 under
-torch.distributed.run (one process per GPU).
+--dump-outputs DIR writes DIR/delays.npy after the timed steps: what the timed
+launches returned, sampled.  The launches fill one delay per request they ran
+into every replica's window; the file holds, for a fixed seeded choice of 32
+replicas that run from the first step on, the delays of the first 1/16 of the
+window, one float64 row per replica.  The streams are seeded, so the same
+arguments give the same requests, and a request's delay does not depend on
+timing; how far a replica gets within the wall-time slices does (by up to a
+quarter of its window between two runs compared), which is why a row stops
+early, at a point the replicas pass in every run: two runs, or two builds,
+write files that can be compared element for element.  A replica that stopped by prime.cpp's rule has zeros
+from there on, the same in every run; the log names any other replica that
+fell short of its row.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full]
+[--dump-outputs DIR]; N>1 under torch.distributed.run (one process per GPU).
 """
 from __future__ import annotations
 
@@ -61,9 +78,12 @@ import json
 import math
 import multiprocessing as mp
 import os
+import queue
 import sys
 import tempfile
+import threading
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -110,6 +130,8 @@ COMPILERS = {1: "hipRTC at run time", 2: "hipcc at build time",
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak (MI355X_MICROARCH.md, chip-level parameters)
 SEED_BASE = 4
 STAGE_GROUP = 256       # replicas whose requests the host generates per staging copy
+DUMP_BYTES = 48 << 20   # --dump-outputs writes at most this much
+DUMP_ROWS = 32          # ... for at most this many replicas
 BUSY_MIN = 0.95         # a replica pool busier than this kept every slot resident for the whole slice
 
 
@@ -118,8 +140,11 @@ def timed_req_bytes(args) -> int:
     return 16 if getattr(args, "req_format", 32) == 16 else REQ_BYTES
 
 
+T_START = time.time()   # log(): seconds since this process imported the file
+
+
 def log(*a):
-    print(*a, file=sys.stderr, flush=True)
+    print(f"[{time.time() - T_START:6.1f}s]", *a, file=sys.stderr, flush=True)
 
 
 def alg_bytes(st: dict, cfg) -> float:
@@ -148,6 +173,41 @@ def busy_guard(pool) -> str | None:
                 f"{pool['replicas'] - pool['replicas_started']} replicas never started: the grid of "
                 f"{pool['wavefronts']} wavefronts was not all resident (pu_resident_replicas overstated)")
     return None
+
+
+def dump_sample(slots: int) -> list:
+    """Replicas whose delays --dump-outputs writes: a seeded choice of up to
+    DUMP_ROWS among the first 1,024 replicas that hold a wavefront from the
+    first timed step on (the same replicas in every run with at least 1,024
+    slots)."""
+    order = np.random.default_rng(SEED_BASE).permutation(1024)
+    return sorted(int(r) for r in order[order < slots][:DUMP_ROWS])
+
+
+def dump_columns(W_t: int, rows: int) -> int:
+    """Requests per row of delays.npy: the first 1/16 of the timed window (the
+    sampled replicas were seen to run 0.45 to 0.8 of the 20-step window),
+    within DUMP_BYTES as float64."""
+    return max(1, min(W_t // 16, DUMP_BYTES // (8 * max(1, rows))))
+
+
+def write_outputs(path: str, kept: dict, sample: list, fill: int, W_t: int) -> tuple:
+    """path/delays.npy: one float64 row per sampled replica with the delays its
+    timed launches returned (kept[r][fill:], after the warmup's) for the first
+    dump_columns() requests of its window, 0 where it ran fewer.  Returns the
+    file's name and the replicas that ran fewer (see the module docstring)."""
+    cols = dump_columns(W_t, len(sample))
+    out = np.zeros((len(sample), cols), dtype=np.float64)
+    short = []
+    for i, r in enumerate(sample):
+        d = kept[r][fill:fill + cols]
+        out[i, :len(d)] = d
+        if len(d) < cols:
+            short.append(r)
+    os.makedirs(path, exist_ok=True)
+    name = os.path.join(path, "delays.npy")
+    np.save(name, out)
+    return name, short
 
 
 def sum_stats(um, replicas: int) -> dict:
@@ -430,45 +490,112 @@ def run_pass(um, args, R: int, rank: int, world: int, dev, stream, replay: int, 
     # hold ~3 GB of host staging in all instead of 6.7 GB per rank
     G = min(R, STAGE_GROUP)
     gens = [P.StreamSet(specs[g:g + G]) for g in range(0, R, G)]
-    host = np.zeros((G, args.chunk), dtype=A.REQ_DTYPE)
     offs = torch.from_numpy((np.arange(R + 1, dtype=np.uint64) * np.uint64(args.chunk)).view(np.int64)).to(dev)
     kept = {r: [] for r in keep}
-
-    def next_chunk(rb: int = REQ_BYTES) -> torch.Tensor:
-        # rb = 16: the chunk as pu_req16 records (pack_req16 refuses what does not fit)
-        out = torch.empty((R, args.chunk * rb), dtype=torch.uint8, device=dev)
-        for k, gen in enumerate(gens):
-            n = len(gen)
-            got = gen.next_into(host[:n])
-            assert got == args.chunk, (got, args.chunk)
-            rec = host[:n] if rb == REQ_BYTES else P.uncore.pack_req16(host[:n])
-            out[k * G:k * G + n].copy_(torch.from_numpy(rec.view(np.uint8).reshape(n, -1)))
-        return out.view(-1)
-
-    d_warm_delay = torch.zeros(R * args.chunk, dtype=torch.int32, device=dev)
-    t_w = time.time()
-    for s in range(args.warmup):
-        d_req = next_chunk()
-        um.run_device(d_req.data_ptr(), offs.data_ptr(), d_warm_delay.data_ptr(), sptr)
-        torch.cuda.synchronize(dev)
-        for r in keep:
-            kept[r].append(d_warm_delay[r * args.chunk:(r + 1) * args.chunk].cpu().numpy())
-        del d_req
-        log(f"[bench] {'closed' if replay else 'open'}-loop warmup step {s} done ({time.time() - t_w:.1f}s)")
-    if os.environ.get("PU_PROF_RESET_AFTER_WARMUP"):   # tools/prof_regions.py: count the timed steps only
-        L = P.uncore.lib()
-        (L.pu_jit_prof_read if os.environ.get("PU_PROF_JIT") else L.pu_engine_prof_read)(None, 0, 1)
-    t_gen = time.time()
     W_t = steps * args.chunk
     # the timed window as 16-B records (--req-format 16): 20 B a request with
     # its delay instead of 36, so the driver's 20-step window fits a replica
     # pool over every resident wavefront in HBM
     rb = timed_req_bytes(args)
+
+    # Staging runs ahead of the warm-up on a thread of its own: the host
+    # generates every chunk (the warm-up's, then the timed window's) group by
+    # group into pinned buffers and copies them to HBM while the warm-up
+    # launches run, so the set-up costs the generation alone.  Two warm-up
+    # chunks are resident at most; the requests and the order of the launches
+    # are those of a serial staging.
+    nthr = host_core_share()
+    pin32 = [torch.empty((G, args.chunk * REQ_BYTES), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+    pin16 = [torch.empty((G, args.chunk * 16), dtype=torch.uint8, pin_memory=True) for _ in range(2)] if rb == 16 else []
+    host32 = [p.numpy().view(A.REQ_DTYPE) for p in pin32]               # [G, chunk] records
+    in_flight = [None, None]                                            # the copy that last read each pinned pair
+    turn = [0]
+    copy_stream = torch.cuda.Stream(dev)
+    packers = ThreadPoolExecutor(nthr) if rb == 16 else None
+    pack = P.uncore.lib().pu_pack_req16
+
+    def fill(out: torch.Tensor, b: int) -> None:
+        """The next chunk of every replica into out [R, chunk * b] (b = 16: as
+        pu_req16 records; pack_req16 refuses what does not fit)."""
+        for k, gen in enumerate(gens):
+            n, i = len(gen), turn[0] & 1
+            turn[0] += 1
+            if in_flight[i] is not None:
+                in_flight[i].synchronize()
+            h = host32[i][:n]
+            got = gen.next_into(h, nthr)
+            assert got == args.chunk, (got, args.chunk)
+            src = pin32[i]
+            if b == 16:
+                src = pin16[i]
+                cut = [n * j // nthr for j in range(nthr + 1)]
+                parts = [(a, z) for a, z in zip(cut[:-1], cut[1:]) if z > a]
+                rcs = packers.map(lambda az: pack(h[az[0]:az[1]].ctypes.data, (az[1] - az[0]) * args.chunk,
+                                                  src[az[0]:az[1]].data_ptr()), parts)
+                if any(rcs):
+                    P.uncore.pack_req16(h)                              # raises, naming the record
+            with torch.cuda.stream(copy_stream):
+                out[k * G:k * G + n].copy_(src[:n], non_blocking=True)
+                in_flight[i] = torch.cuda.Event()
+                in_flight[i].record(copy_stream)
+
+    warm_free, warm_ready = queue.Queue(), queue.Queue()
+    for _ in range(min(2, args.warmup)):
+        warm_free.put(torch.empty((R, args.chunk * REQ_BYTES), dtype=torch.uint8, device=dev))
+    staged = {"error": None, "t_end": 0.0, "window": queue.Queue()}
+
+    def stage_all() -> None:
+        try:
+            torch.cuda.set_device(dev)
+            for _ in range(args.warmup):
+                buf = warm_free.get()
+                fill(buf, REQ_BYTES)
+                copy_stream.synchronize()
+                warm_ready.put(buf)
+            tmp = torch.empty((R, args.chunk * rb), dtype=torch.uint8, device=dev)
+            d_win = staged["window"].get()
+            for k in range(steps):
+                fill(tmp, rb)
+                with torch.cuda.stream(copy_stream):
+                    d_win[:, k * args.chunk:(k + 1) * args.chunk, :] = tmp.view(R, args.chunk, rb)
+            copy_stream.synchronize()
+            staged["t_end"] = time.time()
+        except BaseException as e:  # noqa: BLE001 — handed to the main thread
+            staged["error"] = e
+            warm_ready.put(None)
+
     d_win = torch.empty((R, W_t, rb), dtype=torch.uint8, device=dev)
-    for k in range(steps):
-        d_win[:, k * args.chunk:(k + 1) * args.chunk, :] = next_chunk(rb).view(R, args.chunk, rb)
+    staged["window"].put(d_win)
+    d_warm_delay = torch.zeros(R * args.chunk, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)                        # zeroed before the engine's stream writes it
+    t_w = time.time()
+    stager = threading.Thread(target=stage_all, name="bench-staging", daemon=True)
+    stager.start()
+    for s in range(args.warmup):
+        d_req = warm_ready.get()
+        if d_req is None:
+            raise staged["error"]
+        um.run_device(d_req.data_ptr(), offs.data_ptr(), d_warm_delay.data_ptr(), sptr)
+        stream.synchronize()
+        for r in keep:
+            kept[r].append(d_warm_delay[r * args.chunk:(r + 1) * args.chunk].cpu().numpy())
+        warm_free.put(d_req)
+        del d_req
+        log(f"[bench] {'closed' if replay else 'open'}-loop warmup step {s} done ({time.time() - t_w:.1f}s)")
+    if os.environ.get("PU_PROF_RESET_AFTER_WARMUP"):   # tools/prof_regions.py: count the timed steps only
+        L = P.uncore.lib()
+        (L.pu_jit_prof_read if os.environ.get("PU_PROF_JIT") else L.pu_engine_prof_read)(None, 0, 1)
+    stager.join()
+    if staged["error"] is not None:
+        raise staged["error"]
+    if packers is not None:
+        packers.shutdown()
     for gen in gens:
         gen.close()
+    while not warm_free.empty():
+        warm_free.get()
+    del pin32, pin16, host32
+    torch.cuda.empty_cache()                           # the warm-up chunks' HBM, before the delays take theirs
     d_win_delay = torch.zeros(R * W_t, dtype=torch.int32, device=dev)
     win_off = np.arange(R + 1, dtype=np.uint64) * np.uint64(W_t)
     d_win_off = torch.from_numpy(win_off.view(np.int64)).to(dev)
@@ -478,9 +605,10 @@ def run_pass(um, args, R: int, rank: int, world: int, dev, stream, replay: int, 
     pool = 0 < slots < R and args.slice_ms > 0
     d_sched = torch.zeros(um.pool_words(slots) if pool else 1, dtype=torch.int32, device=dev)
     torch.cuda.synchronize(dev)
-    log(f"[bench] timed requests resident: {R} x {W_t} in {time.time() - t_gen:.1f}s"
+    log(f"[bench] timed requests resident: {R} x {W_t}, {staged['t_end'] - t_w:.1f}s after the staging began"
         + (f"; replica pool: {slots} wavefronts over {R} replicas" if pool else ""))
     before = sum_stats(um, R)
+    log("[bench] counters read")
     per_before = [um.stats(r).as_dict() for r in range(R)] if os.environ.get("PU_PROF_RESET_AFTER_WARMUP") else None
 
     # HIP events on the engine's (non-null) stream time exactly its launches
@@ -534,6 +662,7 @@ def run_pass(um, args, R: int, rank: int, world: int, dev, stream, replay: int, 
     for r in keep:
         kept[r].append(d_win_delay[r * W_t:r * W_t + int(adv[r])].cpu().numpy())
     after = sum_stats(um, R)
+    log("[bench] counters read")
     per_replica = None
     if per_before is not None:
         per_after = [um.stats(r).as_dict() for r in range(R)]
@@ -665,8 +794,16 @@ def parse_args(argv=None):
                          "(0 = no parity at N > 1)")
     ap.add_argument("--closed-steps", type=int, default=5, help="timed steps of the closed-loop pass (0 = skip)")
     ap.add_argument("--single-requests", type=int, default=40960)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else this file measures or checks: the parity of "
+                         "the GPU's delays against the reference, the CPU baselines, the closed-loop pass and one "
+                         "simulation alone (a plain run sets up, warms up, times --steps steps and prints its line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the delays the timed launches returned for a fixed sample of "
+                         "replicas to DIR/delays.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no reference processes and no CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: no closed-loop pass and no single simulation (profiling runs)")
     ap.add_argument("--config", choices=sorted(WORKLOADS), default="C4",
                     help="SURVEY.md §8d shape: C4 (1024 cores) is the metric's; C3 (256 cores, 3 levels) and C5 "
                          "(4096 cores) are measured the same way")
@@ -749,7 +886,9 @@ def main(argv=None) -> None:
         log(f"[bench] --gpus {args.gpus} but WORLD_SIZE={world}: refusing to report a {world}-rank run "
             f"as {args.gpus} GPUs")
         sys.exit(2)
-    extras = rank == 0 and world == 1 and not args.no_extras
+    # a plain run is the headline alone; --full adds every other pass and check
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras
+    cpu_on = args.full and not args.no_cpu
 
     import primesim_amd as P
     from primesim_amd import _abi as A
@@ -769,8 +908,8 @@ def main(argv=None) -> None:
     # at N>1 a few per rank, replaying this rank's replica 0 and first pool
     # spare (parity of every rank's line)
     ens = None
-    rank_parity = world > 1 and not args.no_cpu and args.rank_parity_workers > 0
-    if (extras and not args.no_cpu) or rank_parity:
+    rank_parity = world > 1 and cpu_on and args.rank_parity_workers > 0
+    if (extras and cpu_on) or rank_parity:
         nw = (args.ensemble_workers or host_core_share()) if extras else args.rank_parity_workers
         ens = Ensemble(xml_path, nw, args.warmup * args.chunk, args.steps * args.chunk, args.ensemble_seconds, rank,
                        ref_mode(args))
@@ -782,15 +921,25 @@ def main(argv=None) -> None:
     local = int(os.environ.get("PU_BENCH_DEVICE", local))
     D = Device(args, cfg, threads, rank, local)
     R, um, dev, stream = D.R, D.um, D.dev, D.stream
+    log(f"[bench] rank {rank}: engine ready")
     global LAST_REPLICAS, LAST_PER_REPLICA
     LAST_REPLICAS = R
     # the ensemble's replicas, spread over 0..R-1: their delays are checked
     # against the reference's bit for bit (replica 0 also by cpu_baseline)
     keep = sorted(set(ens.assign(R, D.slots)) | {0}) if ens is not None else [0]
+    sample = dump_sample(D.slots) if args.dump_outputs and rank == 0 else []
+    keep = sorted(set(keep) | set(sample))
 
     # ---- headline: open-loop replay
     H = D.headline(args, rank, world, keep)
     LAST_PER_REPLICA = H.per_replica
+    if sample:
+        name, short = write_outputs(args.dump_outputs, H.kept, sample, args.warmup * args.chunk,
+                                    args.steps * args.chunk)
+        short = [r for r in short if not um.error_flags(R)[r] & A.PU_ERRF_NEG_DELAY]
+        log(f"[bench] --dump-outputs: {len(sample)} replicas -> {name}"
+            + (f"; replicas {short} had not run their row's requests when the last step ended: their rows' "
+               f"ends depend on this run's timing" if short else ""))
     t_max, tot_processed = reduce_run(H.elapsed, H.processed, D.reduce_device(args))
     _, tot_replicas = reduce_run(0.0, R, D.reduce_device(args))
     _, tot_slots = reduce_run(0.0, D.slots, D.reduce_device(args))
@@ -842,7 +991,7 @@ def main(argv=None) -> None:
             C = run_pass(um, args, R, rank, world, dev, stream, P.uncore.PU_REPLAY_CLOSED, args.closed_steps,
                          [0], D.slots)
             c_par, c_cpu = None, None
-            if not args.no_cpu:
+            if cpu_on:
                 import oracle as O
                 w0, n_t = args.warmup * args.chunk, args.closed_steps * args.chunk
                 s0 = P.generate_stream(stream_spec(replica_seed(SEED_BASE, 0, 0), w0 + n_t))
@@ -890,7 +1039,7 @@ def main(argv=None) -> None:
             closed["single_instance"] = single_instance(cfg, args, dev, threads, P.uncore.PU_REPLAY_CLOSED)
             log(f"[bench] closed-loop single instance: {closed['single_instance']['value']:.0f} accesses/s")
         cpu = None
-        if not args.no_cpu and world == 1:          # the CPU baseline runs at N=1 only
+        if cpu_on and world == 1:          # the CPU baseline runs at N=1 only
             # replica 0's stream: the reference fills the warmup untimed, then is
             # timed on the requests of the GPU's timed window (as many as fit in
             # --cpu-seconds); parity is checked on every request both ran
@@ -989,10 +1138,11 @@ def main(argv=None) -> None:
             "cpu_baseline_ensemble": ens_res if world == 1 else None,
             "replica_parity": replica_parity_res,
             "rank_parity": ranks_parity,
-            "parity": parity_ok if (not args.no_cpu and (world == 1 or ranks_parity is not None)) else None,
+            "parity": parity_ok if (cpu_on and (world == 1 or ranks_parity is not None)) else None,
             "busy_guard": busy_err or f"ok: replica-pool busy fraction >= {BUSY_MIN} (or the pool ran dry)",
         }
         print(json.dumps(result), flush=True)
+        log("[bench] result line printed")
     else:
         um.close()
     try:

@@ -79,3 +79,21 @@ def test_ensemble_returns_the_delays_of_its_replicas(tmp_path):
             ref.alloc_core(prog, th)
         want, _ = ref.run(reqs)
         np.testing.assert_array_equal(got, want[:len(got)])
+
+
+def test_dump_outputs_sample_and_file(tmp_path):
+    """--dump-outputs: a fixed sample of slot replicas, each row the first
+    requests of its replica's timed window, zeros where the replica ran fewer."""
+    sample = bench.dump_sample(7168)
+    assert sample == bench.dump_sample(5120) == sorted(set(sample))       # the same for any >= 1,024 slots
+    assert len(sample) == 32 and all(0 <= r < 1024 for r in sample)
+    assert bench.dump_sample(2) == [0, 1]
+    assert bench.dump_columns(20 * 40960, 32) == 51200
+    assert 32 * bench.dump_columns(10 ** 9, 32) * 8 <= 64 << 20           # a long window: truncated rows
+    fill, W_t = 5, 64
+    kept = {0: np.arange(fill + 40, dtype=np.int32), 3: np.arange(100, 100 + fill + 3, dtype=np.int32)}
+    name, short = bench.write_outputs(str(tmp_path / "out"), kept, [0, 3], fill, W_t)
+    out = np.load(name)
+    assert name.endswith("delays.npy") and out.dtype == np.float64 and out.shape == (2, 4)
+    assert np.array_equal(out[0], [5, 6, 7, 8])
+    assert np.array_equal(out[1], [105, 106, 107, 0]) and short == [3]    # 3 run: the row's end is empty

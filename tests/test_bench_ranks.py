@@ -53,9 +53,21 @@ def bench_peak():
 
 
 # the stub's ranks run 1,200 requests per replica: the reference processes
-# fill 600 (the "warmup") and replay the next 600 (the "timed window")
-PARITY_ARGS = ["--gpus", "2", "--dist-backend", "gloo", "--steps", "1", "--warmup", "1", "--chunk", "600",
-               "--ensemble-seconds", "2"]
+# fill 600 (the "warmup") and replay the next 600 (the "timed window");
+# the per-rank parity is one of the checks behind --full
+PLAIN_ARGS = ["--gpus", "2", "--dist-backend", "gloo", "--steps", "1", "--warmup", "1", "--chunk", "600",
+              "--ensemble-seconds", "2"]
+PARITY_ARGS = [*PLAIN_ARGS, "--full"]
+
+
+def test_a_plain_run_starts_no_reference_processes(tmp_path):
+    """Without --full the line is the headline alone: no parity, no baseline."""
+    r = _run(PLAIN_ARGS, tmp_path)
+    assert r.returncode == 0, r.stderr[-3000:]
+    b = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert b["n_gpus"] == 2 and b["steps"] == 1 and b["ms_per_step"] == 1.5e3
+    assert b["parity"] is None and b["rank_parity"] is None and b["cpu_baseline"] is None
+    assert "cpu ensemble" not in r.stderr
 
 
 def test_two_ranks_check_their_replicas_against_the_reference(tmp_path):

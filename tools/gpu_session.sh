@@ -10,9 +10,9 @@
 #   smoke        __graft_entry__.smoke()
 #   latency      tools/latency_bench.py: uncore_access and one message per call, resident kernel vs a launch per call
 #   traffic      PMC fabric traffic of the headline kernel on the driver's window (tools/pmc_traffic.py)
-#   bench        bench.py on the driver's config (--steps 20 --warmup 5), carrying TAG_traffic.json if present
-#   bench_default  bench.py with no flags
-#   bench_c3 / bench_c5  bench.py --config C3 / C5 on the driver's window (C5 closed loop by default)
+#   bench        bench.py --full on the driver's config (--steps 20 --warmup 5), carrying TAG_traffic.json if present
+#   bench_default  bench.py --full with no other flags
+#   bench_c3 / bench_c5  bench.py --full --config C3 / C5 on the driver's window (C5 closed loop by default)
 #   rocprof      rocprofv3 --kernel-trace --stats of the driver's config (headline only)
 #   sq           SQ wave-state / instruction counters of the headline kernel (tools/pmc_sq.py)
 #   sq_closed / traffic_closed / regions_closed  the headline kernel's SQ counters, fabric traffic and region
@@ -23,7 +23,7 @@
 #   tworank      bench.py --gpus 2 with both ranks on card 0 (gloo)
 #   sweep        tools/relax/sweep_bench: one relaxation sweep's phases L and F on the GPU, W = 1,024 and 4,096
 #                (inputs from tools/relax/make_sweeps.sh), plus its rocprofv3 kernel stats
-#   tworank_parity  the same with each rank's reference parity processes and the job-level roofline
+#   tworank_parity  the same with --full: each rank's reference parity processes and the job-level roofline
 #   regions_single  lone-wave region profiles of the shipped compiled-configuration latency kernel
 #                (-DPU_PROF through PRIMEUNCORE_JIT_EXTRA), open and closed loop
 #   regions_ens  the same for the throughput kernel at the headline's replica count
@@ -87,10 +87,10 @@ for S in "$@"; do
     smoke) timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > ${O}_smoke.log 2>&1 || exit 1;;
     traffic) timeout -k 10 500 python tools/pmc_traffic.py --work /tmp/pmc --out ${O}_traffic.json -- $DRIVER --no-cpu --no-extras > ${O}_traffic.log 2>&1 || exit 1;;
     bench) TJ=""; [ -f ${O}_traffic.json ] && TJ="--traffic-json ${O}_traffic.json"
-           timeout -k 10 400 $BENCH $DRIVER $TJ > ${O}_bench.json 2> ${O}_bench.log || exit 1;;
-    bench_c3) timeout -k 10 500 $BENCH --config C3 $DRIVER > ${O}_bench_c3.json 2> ${O}_bench_c3.log || exit 1;;
-    bench_c5) timeout -k 10 600 $BENCH --config C5 $DRIVER > ${O}_bench_c5.json 2> ${O}_bench_c5.log || exit 1;;
-    bench_default) timeout -k 10 400 $BENCH > ${O}_bench_default.json 2> ${O}_bench_default.log || exit 1;;
+           timeout -k 10 400 $BENCH $DRIVER --full $TJ > ${O}_bench.json 2> ${O}_bench.log || exit 1;;
+    bench_c3) timeout -k 10 500 $BENCH --config C3 $DRIVER --full > ${O}_bench_c3.json 2> ${O}_bench_c3.log || exit 1;;
+    bench_c5) timeout -k 10 600 $BENCH --config C5 $DRIVER --full > ${O}_bench_c5.json 2> ${O}_bench_c5.log || exit 1;;
+    bench_default) timeout -k 10 400 $BENCH --full > ${O}_bench_default.json 2> ${O}_bench_default.log || exit 1;;
     rocprof) TJ=""; [ -f ${O}_traffic.json ] && TJ="--traffic-json ${O}_traffic.json"
              timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${T}_prof -o run -- python3 bench.py $DRIVER --no-cpu --no-extras $TJ > ${O}_bench_under_rocprof.json 2> ${O}_rocprof.log || exit 1
              cp /tmp/${T}_prof/run_kernel_stats.csv ${O}_kernel_stats.csv || exit 1;;
@@ -103,7 +103,7 @@ for S in "$@"; do
     rcp) timeout -k 10 120 tools/probe/rcp_probe 4096 > ${O}_rcp.json 2> ${O}_rcp.log || exit 1;;
     handoff) timeout -k 10 120 tools/probe/handoff > ${O}_handoff.json 2> ${O}_handoff.log || exit 1;;
     tworank) PU_BENCH_DEVICE=0 timeout -k 10 300 $BENCH --gpus 2 --steps 3 --warmup 2 --no-cpu --dist-backend gloo > ${O}_two_rank.json 2> ${O}_two_rank.log || exit 1;;
-    tworank_parity) PU_BENCH_DEVICE=0 timeout -k 10 400 $BENCH --gpus 2 --steps 3 --warmup 2 --dist-backend gloo > ${O}_two_rank_parity.json 2> ${O}_two_rank_parity.log || exit 1;;
+    tworank_parity) PU_BENCH_DEVICE=0 timeout -k 10 400 $BENCH --gpus 2 --steps 3 --warmup 2 --full --dist-backend gloo > ${O}_two_rank_parity.json 2> ${O}_two_rank_parity.log || exit 1;;
     sweep) for W in 1024 4096; do
              timeout -k 10 120 tools/relax/sweep_bench tools/relax/data/w$W 200 > ${O}_sweep_w$W.json 2> ${O}_sweep_w$W.log || exit 1
            done
