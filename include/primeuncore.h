@@ -254,25 +254,22 @@ void       pu_destroy(pu_handle* h);
  * can be specialised against (compile-time configuration).  Returns the full
  * length like snprintf; no reference counterpart. */
 long pu_config_geo_source(const pu_sim_cfg* cfg, char* buf, size_t cap);
-/* Compile-time configuration.  pu_create compiles the engine kernel for the
+/* Compile-time configuration.  pu_create compiles the engine kernels for the
  * configuration's geometry with hipRTC (every cache/mesh/latency value a
  * constant) and launches that code object; compiled code objects are cached on
- * disk (PRIMEUNCORE_JIT_CACHE, else jit_cache/ beside the library).
- * PRIMEUNCORE_JIT=0, or a failed compile, runs the library's ahead-of-time
- * kernels (the same engine source for a runtime geometry).  No reference
- * counterpart (the reference's System reads its XmlSys at run time).
+ * disk (PRIMEUNCORE_JIT_CACHE, else jit_cache/ beside the library).  These
+ * are the library's only engine kernels: when the compile or the load fails,
+ * pu_create fails and pu_last_error() carries the compiler's log.  No
+ * reference counterpart (the reference's System reads its XmlSys at run time).
  * pu_config_jit_warm compiles into the cache without a GPU (1: was cached,
- * 0: compiled, PU_E* on failure); pu_compiled_config tells what handle h
- * runs: 2 the compiled configuration for every launch (the default); 1 the
- * compiled configuration for latency launches (at most one replica per CU,
- * headers in LDS) and the ahead-of-time kernels for throughput launches
- * (PRIMEUNCORE_JIT_THROUGHPUT=0; sets wider than 64 ways always take 2);
- * 0 the ahead-of-time kernels only.  pu_compiled_compiler tells which
- * compiler built the two code objects (throughput and latency kernels) handle
- * h runs: 2 hipcc for both (written by pu_config_jit_warm in a process that
- * set PRIMEUNCORE_JIT_OFFLINE=1 and has not used the GPU: the build-time
- * warm-up, tools/jit_warm.py), 1 hipRTC for both (cache misses at run time),
- * 3 one of each, 0 none. */
+ * 0: compiled, PU_E* on failure).  pu_compiled_config returns 2 (the
+ * compiled configuration runs every launch) for any handle and 0 for NULL;
+ * other values belonged to kernels the library no longer has.
+ * pu_compiled_compiler tells which compiler built the two code objects
+ * (throughput and latency kernels) handle h runs: 2 hipcc for both (written
+ * by pu_config_jit_warm in a process that set PRIMEUNCORE_JIT_OFFLINE=1 and
+ * has not used the GPU: the build-time warm-up, tools/jit_warm.py), 1 hipRTC
+ * for both (cache misses at run time), 3 one of each, 0 none. */
 int pu_config_jit_warm(const pu_sim_cfg* cfg);
 int pu_compiled_config(const pu_handle* h);
 int pu_compiled_compiler(const pu_handle* h);
@@ -281,8 +278,8 @@ int pu_compiled_compiler(const pu_handle* h);
  * code objects whose prefix some library still carries). */
 const char* pu_jit_source_tag(void);
 
-/* Diagnostics, no reference counterpart (tools/prof_regions.py --jit): the
- * region cycle counters of the loaded compiled-configuration kernels built
+/* Diagnostics, no reference counterpart (tools/prof_regions.py): the
+ * region cycle counters of the loaded engine kernels built
  * with PRIMEUNCORE_JIT_EXTRA=-DPU_PROF, summed over modules into out[0..n);
  * reset != 0 clears them.  Returns n, 0 when no loaded kernel counts regions,
  * < 0 on error. */

@@ -40,30 +40,29 @@
 
 namespace {
 
-// Compile-time configuration (jit.cpp): built with -DPU_JIT_GEO='"file"', a file
-// written by pu_config_geo_source (`__device__ constexpr Geo kJitGeo = {...};`
-// and `#define PU_JIT_NL <levels>`), only the kernels of that one
-// configuration are emitted and they read their geometry from the constant,
-// so every configuration value folds into the code.
+// This file is compiled in two ways.
+//  * The engine kernels (PU_JIT_KERNEL, at the end): jit.cpp compiles them once
+//    per configuration with -DPU_JIT_GEO='"file"', a file written by
+//    pu_config_geo_source (`__device__ constexpr Geo kJitGeo = {...};` and
+//    `#define PU_JIT_NL <levels>`).  Only the kernels of that one
+//    configuration are emitted and they read their geometry from the
+//    constant, so every configuration value folds into the code.  These are
+//    the only engine kernels.
+//  * The library's own build, without PU_JIT_GEO: nothing but
+//    init_queues_kernel, init_pool_kernel, the three unit-test hook kernels
+//    (one wave on the queue model / the network / the M/G/1 formula, with a
+//    Geo read through a pointer at run time) and their host launchers.  Every
+//    `#else` of an `#ifdef PU_JIT_GEO` below is what the unit hooks get.
 #ifdef PU_JIT_GEO
 #include PU_JIT_GEO
 #endif
-// Tool builds only (tools/build_exp.sh: profiling, experiments): the
-// ahead-of-time kernels on one configuration's constant geometry.
-#if defined(PU_FIXED_GEO) && !defined(PU_JIT_GEO)
-#include PU_FIXED_GEO
-#define PU_AOT_GEO(g) (&kJitGeo)
-#else
-#define PU_AOT_GEO(g) (g)
-#endif
 
-
-// Compiled configuration, throughput kernel: the replica-layout offsets reach
-// the code as opaque scalars (every other geometry value stays a constant).
-// Folded into the address arithmetic they cost the 96-VGPR kernel 17 VGPRs
-// spilled to scratch (opaque: 4; the latency kernel, with registers to spare,
-// keeps them folded): +4.6% on the C4 headline against the ahead-of-time
-// kernel, same box (profiles/r3o_ab_opq.txt).
+// Throughput kernel: the replica-layout offsets reach the code as opaque
+// scalars (every other geometry value stays a constant).  Folded into the
+// address arithmetic they cost the 96-VGPR kernel 17 VGPRs spilled to scratch
+// (opaque: 4; the latency kernel, with registers to spare, keeps them
+// folded): +4.6% on the C4 headline against the same kernel reading a
+// run-time Geo, same box (profiles/r3o_ab_opq.txt).
 template <bool LH, int NL, class T>
 __device__ __forceinline__ T off_v(T c) {
 #ifdef PU_JIT_GEO
@@ -158,16 +157,6 @@ struct SetView {
     uint32_t w0;      // first way of the chunk held
 };
 
-// Sets wider than 64 ways (walked in 64-way chunks, way order) are compiled
-// into configuration-specific kernels only (jit.cpp: the geometry is a
-// constant, so narrower configurations carry none of that code); pu_create
-// refuses them for the ahead-of-time kernels.
-#if defined(PU_JIT_GEO) || defined(PU_FIXED_GEO)
-constexpr bool kWideSets = true;
-#else
-constexpr bool kWideSets = false;
-#endif
-
 // A queue's ring as held by the wave, in logical order: lane l holds the
 // live intervals l and l+64 counted from the ring cursor (physical slots
 // (head + l) & 127 and (head + 64 + l) & 127), so the search's hit mask needs no
@@ -193,7 +182,7 @@ struct QState {
 #ifndef PU_RING_PF
 #define PU_RING_PF 3   // staged rings in flight per wave (6 KB LDS: 5 waves/SIMD fit the CU's 160 KB)
 #endif
-// The throughput kernels' own count.  The compiled one-level configuration
+// The throughput kernels' own count.  The one-level configuration
 // runs 7 waves per SIMD with 1 staged ring: 3,376 B of LDS per wave = three
 // 1,280-B units, so all 28 waves of a CU reside.  6 waves with 2 rings (five
 // units, 25 per CU) was +4.0% on the C4 headline against 5 waves with 3 rings
@@ -204,36 +193,11 @@ struct QState {
 #if defined(PU_JIT_GEO) && PU_JIT_NL == 1
 #define PU_RING_PF_TP 1
 #else
-#define PU_RING_PF_TP PU_RING_PF
+#define PU_RING_PF_TP PU_RING_PF   // deeper hierarchies, and the unit hooks
 #endif
 #endif
 template <bool LH>
 constexpr int ring_pf() { return LH ? PU_RING_PF : PU_RING_PF_TP; }
-// Waves per SIMD the kernel is compiled for (the register budget: 5 waves =
-// 96 VGPRs).  The one-level engine fits 96 with a 5-VGPR spill (once the
-// pool/page-table state moved to LDS) and runs 2.9% faster at 5 resident
-// waves than at 4 (120 VGPRs, no spill; same-box A/B); the deeper hierarchies
-// would spill ~120 VGPRs at 128, so they keep the compiler's choice.
-#ifndef PU_WAVES_1LEVEL
-#if defined(PU_JIT_GEO)
-#define PU_WAVES_1LEVEL 7   // compiled configuration: 72 VGPRs, one 4-B spill (jit.cpp's options)
-#else
-#define PU_WAVES_1LEVEL 5
-#endif
-#endif
-// Deeper hierarchies (NL > 1), compiled configuration: 4 waves per SIMD (128
-// VGPRs, no spill at C3, where the compiler's own choice was 150 VGPRs = 3
-// waves): C3 +20% (448.1 / 449.4 vs 373.4 / 373.2 M/s; 5 waves, 31 VGPRs
-// spilled, +13%; profiles/r6e_ab_c3.txt, same box).  The ahead-of-time
-// kernels keep the compiler's choice.
-#ifndef PU_WAVES_DEEP
-#if defined(PU_JIT_GEO)
-#define PU_WAVES_DEEP 4
-#else
-#define PU_WAVES_DEEP 1
-#endif
-#endif
-#define PU_MIN_WAVES(NL) ((NL) == 1 ? PU_WAVES_1LEVEL : PU_WAVES_DEEP)
 // native vectors (not classes), so loads/stores through global-address-space
 // pointers need no conversion: slot = {first, second}, header = 10 dwords
 typedef unsigned long long v2u64 __attribute__((ext_vector_type(2)));
@@ -245,18 +209,17 @@ typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
 // transmit adds its six network sums at once (lanes 0-5); the router, link and
 // inject delay totals are derived from them at the flush (Network::transmit's
 // per-packet terms are linear in them, network.cpp:146-156).
-// The compiled configuration of a configuration without verbose_report
-// (Geo.cnt_sum) also keeps the per-level {ins, miss, evict, wb} sums here
+// A configuration without verbose_report (Geo.cnt_sum) also keeps the per-level {ins, miss, evict, wb} sums here
 // (SN_CNT0 + 4 * level + k; levels 0-3, PU_CNT_DIR, PU_CNT_TLB) instead of
 // one device-scope atomic per event on a per-cache counter: those atomics
 // bypass the XCD's L2 to the memory side (4.55 per access at C4,
 // TCC_EA0_WRREQ_ATOMIC_DRAM_32B) and sit in the wave's in-order vector
 // memory queue.  Only the verbose report lists caches one by one
-// (system.cpp:1020-1069); the ahead-of-time kernels keep per-cache counters.
+// (system.cpp:1020-1069) and keeps per-cache counters.
 #if defined(PU_JIT_GEO)
 constexpr bool kCntSum = kJitGeo.cnt_sum != 0;
 #else
-constexpr bool kCntSum = false;
+constexpr bool kCntSum = false;   // the unit hooks count no cache events
 #endif
 enum StatId {
     SN_ACC, SN_DIST, SN_TOTAL, SN_PLEN, SN_FLITS, SN_MG1, SN_DRAM, SN_BUSCONT,
@@ -276,14 +239,14 @@ static __shared__ unsigned long long lds_stat[SN_COUNT];
 constexpr int alive_base(int l) { return l <= 0 ? 0 : alive_base(l - 1) + kJitGeo.lv[l - 1].ncaches; }
 constexpr bool kAliveLds = kCntSum && PU_ALIVE_LDS && alive_base(PU_JIT_NL) <= 4096;
 constexpr int kAliveWords = kAliveLds ? (alive_base(PU_JIT_NL) + 31) / 32 : 1;
-#else
+#else   // the unit hooks touch no cache
 constexpr int alive_base(int) { return 0; }
 constexpr bool kAliveLds = false;
 constexpr int kAliveWords = 1;
 #endif
 static __shared__ uint32_t lds_alive[kAliveWords];
 static __shared__ unsigned long long lds_err;
-// The message loop's state (uncore_kernel), lane 0 its writer.
+// The message loop's state (uncore_body), lane 0 its writer.
 struct LoopCtl {
     int64_t msg_shift;     // PU_KF_CLOSED: core shift at the open message's start
     uint64_t dead_tags;    // PU_KF_MSGHALT: receive threads that have exited
@@ -365,8 +328,9 @@ __device__ __forceinline__ void err_or(uint64_t f) {
     }
 }
 
-// Region cycle counters, compiled in only with -DPU_PROF (the profiling build,
-// libprimeuncore_prof.so; tools/prof_regions.py).  Regions are inclusive.
+// Region cycle counters, compiled in only with -DPU_PROF (a diagnostic option
+// of the configuration's compile: PRIMEUNCORE_JIT_EXTRA, tools/prof_regions.py).
+// Regions are inclusive.
 enum ProfId {
     PF_LOOP, PF_REQ, PF_NET, PF_NSETUP, PF_NHOPS, PF_NTREE, PF_NWAIT, PF_NWB, PF_SETL0, PF_SETLN, PF_HOME_LD,
     PF_HOME, PF_DOWN, PF_WINDOWS, PF_TREEHOPS, PF_DEMAND, PF_T_LDS, PF_T_SEARCH, PF_T_DECIDE, PF_T_EDIT,
@@ -376,12 +340,9 @@ enum ProfId {
 #ifdef PU_PROF
 static __shared__ unsigned long long lds_prof[PF_COUNT];
 }  // namespace
-// (outside the anonymous namespace: a compiled-configuration module exports
-// them by name, jit.cpp's jit_prof_read)
+// (outside the anonymous namespace: the code object exports it by name,
+// jit.cpp's jit_prof_read)
 __device__ unsigned long long g_prof[PF_COUNT];
-// per-replica (block) wall-clock stamps of the last launch and summed durations
-#define PU_PROF_BLOCKS 4096
-__device__ unsigned long long g_blk_t0[PU_PROF_BLOCKS], g_blk_t1[PU_PROF_BLOCKS], g_blk_dur[PU_PROF_BLOCKS];
 namespace {
 #define PROF_T(v) const uint64_t v = __builtin_amdgcn_s_memtime()
 #define PROF_ADD(id, t0) \
@@ -1549,7 +1510,9 @@ struct Engine {
             v.mts = INT64_MAX;
         }
     }
-    static __device__ __forceinline__ bool wide(uint64_t nways) { return kWideSets && nways > 64; }
+    // sets wider than 64 ways are walked in 64-way chunks, way order (the
+    // geometry is a constant, so narrower configurations carry none of that code)
+    static __device__ __forceinline__ bool wide(uint64_t nways) { return nways > 64; }
     // the lane holding `way` (a way of the chunk held)
     static __device__ __forceinline__ int wl(const SetView& v, int way) { return way - (int)v.w0; }
     // Cache::accessLine (cache.cpp:184-202): the first matching way
@@ -2798,9 +2761,6 @@ __device__ __forceinline__ bool replica_run(Engine<NL, LH>& e, char* __restrict_
             lds_main_done = 0;
         }
     }
-#ifdef PU_PROF
-    const uint64_t blk_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
     const uint64_t b = pos ? pos[ix] : off[ix], end = off[ix + 1];
     const bool done = replica_loop<NL, SLICED, LH>(e, reqs, delays, b, end, pos ? pos + ix : nullptr, deadline, flags);
     if constexpr (LH) {                                   // the headers back
@@ -2809,14 +2769,6 @@ __device__ __forceinline__ bool replica_run(Engine<NL, LH>& e, char* __restrict_
         hdr_image_out(e.base + OFF(e.g->off_qhdr), (uint32_t)e.g->nqueues, (uint32_t)e.ln);
     }
     replica_close<NL, LH>(e);
-#ifdef PU_PROF
-    if (e.ln == 0 && blockIdx.x < PU_PROF_BLOCKS) {
-        const uint64_t blk_t1 = __builtin_amdgcn_s_memrealtime();
-        g_blk_t0[blockIdx.x] = blk_t0;
-        g_blk_t1[blockIdx.x] = blk_t1;
-        g_blk_dur[blockIdx.x] += blk_t1 - blk_t0;
-    }
-#endif
     return done;
 }
 
@@ -3099,19 +3051,25 @@ __device__ __forceinline__ void uncore_body(const Geo* __restrict__ g, char* __r
   }
 }
 
-#ifndef PU_JIT_GEO
-template <int NL, int MODE, bool LH = false>
-__global__ __launch_bounds__(LH ? 128 : 64) __attribute__((amdgpu_waves_per_eu(LH ? 1 : PU_MIN_WAVES(NL)))) void uncore_kernel(
-    const Geo* __restrict__ g, char* __restrict__ arena, int replica0, const pu_req* __restrict__ reqs,
-    const uint64_t* __restrict__ off, int32_t* __restrict__ delays, uint64_t* __restrict__ pos, uint64_t budget_ticks,
-    uint32_t flags, uint32_t* __restrict__ sched, int nrep) {
-    uncore_body<NL, MODE, LH>(PU_AOT_GEO(g), arena, replica0, reqs, off, delays, pos, budget_ticks, flags, sched,
-                                nrep);
-}
-#else
+#ifdef PU_JIT_GEO
 }  // namespace
-// Compile-time configuration (jit.cpp): the four launch shapes of this one
-// configuration, unmangled so the host finds them by name in the code object.
+// The engine kernels (jit.cpp): the launch shapes of this one configuration,
+// unmangled so the host finds them by name in the code object.
+//
+// Waves per SIMD they are compiled for (the register budget).  One level: 7
+// waves, 72 VGPRs and one 4-B spill with jit.cpp's options (5 waves = 96
+// VGPRs with a 5-VGPR spill ran 2.9% faster than 4 = 120 VGPRs and no spill,
+// same-box A/B; 6 and 7 since, see PU_RING_PF_TP).  Deeper hierarchies
+// (NL > 1): 4 waves (128 VGPRs, no spill at C3, where the compiler's own
+// choice was 150 VGPRs = 3 waves): C3 +20% (448.1 / 449.4 vs 373.4 / 373.2
+// M/s; 5 waves, 31 VGPRs spilled, +13%; profiles/r6e_ab_c3.txt, same box).
+#ifndef PU_WAVES_1LEVEL
+#define PU_WAVES_1LEVEL 7
+#endif
+#ifndef PU_WAVES_DEEP
+#define PU_WAVES_DEEP 4
+#endif
+#define PU_MIN_WAVES(NL) ((NL) == 1 ? PU_WAVES_1LEVEL : PU_WAVES_DEEP)
 #define PU_JIT_KERNEL(NAME, S, H)                                                                                  \
     extern "C" __global__ __launch_bounds__(H ? 128 : 64) __attribute__((amdgpu_waves_per_eu(H ? 1 : PU_MIN_WAVES(PU_JIT_NL)))) \
     void NAME(const Geo* __restrict__ g, char* __restrict__ arena, int replica0, const pu_req* __restrict__ reqs,     \
@@ -3122,7 +3080,7 @@ __global__ __launch_bounds__(LH ? 128 : 64) __attribute__((amdgpu_waves_per_eu(L
     }
 // PU_JIT_PART 0: the throughput kernels (one wave per replica), 1: the
 // latency kernels (headers in LDS + the M/G/1 helper); jit.cpp compiles each
-// part with its own options.  Undefined: all five (offline tools).
+// part with its own options.  Undefined: all of them (offline tools).
 #if !defined(PU_JIT_PART) || PU_JIT_PART == 0
 PU_JIT_KERNEL(pu_jit_uncore_s0_h0, 0, false)
 PU_JIT_KERNEL(pu_jit_uncore_s1_h0, 1, false)
@@ -3134,9 +3092,8 @@ PU_JIT_KERNEL(pu_jit_uncore_s1_h1, 1, true)
 PU_JIT_KERNEL(pu_jit_uncore_s3_h1, 3, true)
 #endif
 namespace {
-#endif
+#else   // the library's own build: the init kernels and the unit-test hooks
 
-#ifndef PU_JIT_GEO
 // Queue records start as the single free interval [0, UINT64_MAX]
 // (QueueModelHistoryTree ctor, queue_model_history_tree.cpp:28).
 // Packed headers (the engine): n = n1 = 0.0, head 0, count 1, newest 0, f0 0;
@@ -3204,9 +3161,6 @@ __global__ __launch_bounds__(64) void unit_network_kernel(const Geo* __restrict_
     }
     __syncthreads();
     e.flush_stats();
-#ifdef PU_PROF
-    if (e.ln < PF_COUNT) atomicAdd(&g_prof[e.ln], lds_prof[e.ln]);
-#endif
 }
 
 // M/G/1 wait (mg1_wait, queue_model_m_g_1.cpp:16-42) of many queue states at
@@ -3277,65 +3231,6 @@ extern "C" int pu_engine_unit_network(const Geo* d_geo, char* base, const int32_
     return hipGetLastError() == hipSuccess ? 0 : PU_EIO;
 }
 
-// ---------------------------------------------------------------- launchers
-extern "C" int pu_engine_launch(const Geo* d_geo, int num_levels, char* arena, int replica0, int nblocks,
-                                const pu_req* reqs, const uint64_t* off, int32_t* delays, uint64_t* pos,
-                                uint64_t budget_ticks, uint32_t flags, int lds_headers, uint32_t* sched, int nrep,
-                                hipStream_t stream) {
-    dim3 grid((unsigned)nblocks), block(lds_headers ? 128 : 64);   // latency mode: + the M/G/1 helper wave
-#define PU_LAUNCH3(L, S, H)                                                                                        \
-    hipLaunchKernelGGL((uncore_kernel<L, S, H>), grid, block, 0, stream, d_geo, arena, replica0, reqs, off, delays,   \
-                       pos, budget_ticks, flags, sched, nrep)
-#define PU_LAUNCH(L)                                                                                              \
-    if (sched) PU_LAUNCH3(L, 2, false);                                                                            \
-    else if (pos) { if (lds_headers) PU_LAUNCH3(L, 1, true); else PU_LAUNCH3(L, 1, false); }                      \
-    else { if (lds_headers) PU_LAUNCH3(L, 0, true); else PU_LAUNCH3(L, 0, false); }
-    switch (num_levels) {
-        case 1: PU_LAUNCH(1); break;
-        case 2: PU_LAUNCH(2); break;
-        case 3: PU_LAUNCH(3); break;
-        case 4: PU_LAUNCH(4); break;
-#undef PU_LAUNCH
-#undef PU_LAUNCH3
-        default: return PU_EINVAL;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : PU_EIO;
-}
-
-// Replicas (one-wave workgroups) of the throughput kernel of launch mode
-// `mode` (1 time-sliced, 2 replica pool) resident per CU at once by
-// hipOccupancy (VGPRs and the LDS ring staging bound it), and the kernel's
-// static LDS bytes (uncore.cpp applies the device's LDS granularity).  A
-// launch of more replicas runs the rest only after resident ones finish.
-template <int NL>
-static hipError_t occ_of(int mode, int* n, int* lds) {
-    hipFuncAttributes a{};
-    hipError_t e;
-    if (mode == 2) {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(n, uncore_kernel<NL, 2>, 64, 0);
-        if (e == hipSuccess) e = hipFuncGetAttributes(&a, (const void*)uncore_kernel<NL, 2>);
-    } else {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(n, uncore_kernel<NL, 1>, 64, 0);
-        if (e == hipSuccess) e = hipFuncGetAttributes(&a, (const void*)uncore_kernel<NL, 1>);
-    }
-    *lds = (int)a.sharedSizeBytes;
-    return e;
-}
-extern "C" int pu_engine_occupancy(int num_levels, int mode, int* blocks_per_cu, int* lds_bytes) {
-    int n = 0, lds = 0;
-    hipError_t e;
-    switch (num_levels) {
-        case 1: e = occ_of<1>(mode, &n, &lds); break;
-        case 2: e = occ_of<2>(mode, &n, &lds); break;
-        case 3: e = occ_of<3>(mode, &n, &lds); break;
-        case 4: e = occ_of<4>(mode, &n, &lds); break;
-        default: return PU_EINVAL;
-    }
-    *blocks_per_cu = n;
-    *lds_bytes = lds;
-    return e == hipSuccess ? 0 : PU_EIO;
-}
-
 // Queue headers of one replica that fit the latency-mode LDS image.
 extern "C" int pu_engine_lds_header_queues(void) { return (int)PU_LDS_Q; }
 
@@ -3349,30 +3244,4 @@ extern "C" int pu_engine_init_queues(char* arena, uint64_t replica_bytes, uint64
     return hipGetLastError() == hipSuccess ? 0 : PU_EIO;
 }
 
-#ifdef PU_PROF
-// Profiling build only: read (and optionally clear) the region counters.
-extern "C" int pu_engine_prof_read(unsigned long long* out, int n, int reset) {
-    if (n > PF_COUNT) n = PF_COUNT;
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (n > 0 && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * n) != hipSuccess)
-        return -1;
-    if (reset) {
-        unsigned long long z[PF_COUNT] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z)) != hipSuccess) return -1;
-        static unsigned long long zb[PU_PROF_BLOCKS];
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_blk_dur), zb, sizeof(zb)) != hipSuccess) return -1;
-    }
-    return n;
-}
-// Per-block stamps (s_memrealtime, 100 MHz) of the last launch and summed durations.
-extern "C" int pu_engine_prof_blocks(unsigned long long* t0, unsigned long long* t1, unsigned long long* dur, int n) {
-    if (n > PU_PROF_BLOCKS) n = PU_PROF_BLOCKS;
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    size_t b = sizeof(unsigned long long) * (size_t)n;
-    if (hipMemcpyFromSymbol(t0, HIP_SYMBOL(g_blk_t0), b) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(t1, HIP_SYMBOL(g_blk_t1), b) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(dur, HIP_SYMBOL(g_blk_dur), b) != hipSuccess) return -1;
-    return n;
-}
-#endif
 #endif  // !__HIPCC_RTC__ && !PU_JIT_OFFLINE

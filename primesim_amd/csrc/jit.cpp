@@ -21,11 +21,10 @@
 // libprimeuncore.so (in-tree, so a cache warmed by __graft_entry__.build()
 // travels with the library; tools/jit_warm.py prunes code objects whose source
 // tag no library in the tree carries).  A cached code object the device
-// refuses is deleted and compiled again once.  PRIMEUNCORE_JIT=0 turns the
-// specialisation off: the library's ahead-of-time kernels (the same engine
-// source compiled for a runtime Geo) run instead, as they do when a compile or
-// a load fails (with a message).  hipRTC itself is a link-time dependency of
-// the library (-lhiprtc), not an optional one.
+// refuses is deleted and compiled again once.  These kernels are the only
+// engine: a compile or a load that fails fails pu_create, with the compiler's
+// log in pu_last_error().  hipRTC itself is a link-time dependency of the
+// library (-lhiprtc), not an optional one.
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <spawn.h>
@@ -131,7 +130,7 @@ std::vector<std::string> options(const std::string& arch, int waves_1level, int 
     // max-occupancy: at C4 the throughput kernel spills 2 VGPRs instead of 4
     // and ran ahead of max-ILP in each of three interleaved rounds (233.0 /
     // 230.0 / 232.7 vs 215.9 / 226.9 / 231.4 M/s), one simulation alone level
-    // (profiles/r3q_ab_occ*.txt); the ahead-of-time kernels keep max-ILP.
+    // (profiles/r3q_ab_occ*.txt).
     // -Werror=missing-field-initializers: a Geo field the emitter (geo_emit.h)
     // forgets would otherwise silently be 0 in the compiled configuration.
     std::vector<std::string> o = {"--offload-arch=" + arch, "-O3", "-std=c++20", "-ffp-contract=off", "-fwrapv",
@@ -331,11 +330,6 @@ constexpr const char* kBuildArch = "gfx950";   // the library's own target (Make
 
 }  // namespace
 
-bool jit_enabled() {
-    const char* e = std::getenv("PRIMEUNCORE_JIT");
-    return !(e && e[0] == '0');
-}
-
 // The engine sources this library embeds, as 8 hex digits: the prefix of
 // every code object name it writes (tools/jit_warm.py keeps the code objects
 // whose prefix a library in the tree carries).
@@ -423,8 +417,8 @@ bool load_module(const std::vector<char>& code, int part, JitKernels* out, std::
 }
 
 // Part `part` of configuration g: from the cache, else compiled into it, then
-// loaded; false after a message (the caller falls back to the ahead-of-time
-// kernels).
+// loaded; false with the reason (the compiler's log included) in
+// pu_last_error().
 bool load_part(const Geo& g, int waves, const std::string& arch, int part, JitKernels* out, bool verbose,
                std::string* key_out) {
     std::vector<char> code;
@@ -450,16 +444,12 @@ bool load_part(const Geo& g, int waves, const std::string& arch, int part, JitKe
     *key_out = key;
     if (verbose) std::fprintf(stderr, "[primeuncore] compiling the engine for this configuration (%s)\n", key.c_str());
     if (compile_into(g, waves, arch, part, kJitRtc, path, &code, &log) != 0) {
-        std::fprintf(stderr,
-                     "[primeuncore] compile-time configuration unavailable (hipRTC failed); the ahead-of-time "
-                     "kernels run instead:\n%s\n",
-                     log.c_str());
+        set_error(PU_EIO, "hipRTC could not compile the engine for this configuration:\n" + log);
         return false;
     }
     if (!load_module(code, part, out, &why)) {
-        std::fprintf(stderr, "[primeuncore] freshly compiled code object %s: %s; the ahead-of-time kernels run "
-                             "instead\n", path.c_str(), why.c_str());
         std::remove(path.c_str());
+        set_error(PU_EIO, "freshly compiled code object " + path + ": " + why);
         return false;
     }
     return true;
@@ -469,7 +459,6 @@ bool load_part(const Geo& g, int waves, const std::string& arch, int part, JitKe
 int jit_load(const Geo& g, JitKernels* out, bool verbose) {
     *out = JitKernels{};
     g_gpu_used = true;
-    if (!jit_enabled()) return 0;
     const int waves = jit_waves();
     const std::string arch = device_arch();
     std::lock_guard<std::mutex> lk(g_jit_mu);   // one compile at a time; another thread may have built it
@@ -477,9 +466,8 @@ int jit_load(const Geo& g, JitKernels* out, bool verbose) {
     for (int part = 0; part < kJitParts; part++)
         if (!load_part(g, waves, arch, part, out, verbose, &key[part])) {
             jit_unload(out);
-            return 0;
+            return PU_EIO;
         }
-    out->ok = true;
     out->key = key[0] + "+" + key[1].substr(key[1].find('-') + 1);
     return 0;
 }
@@ -546,8 +534,8 @@ void jit_unload(JitKernels* k) {
 }
 
 // Diagnostics: the region counters (g_prof) of every loaded module compiled
-// with -DPU_PROF (PRIMEUNCORE_JIT_EXTRA), summed; optionally cleared with the
-// per-block durations.  Returns n, or 0 when no loaded module has them.
+// with -DPU_PROF (PRIMEUNCORE_JIT_EXTRA), summed and optionally cleared.
+// Returns n, or 0 when no loaded module has them.
 int jit_prof_read(unsigned long long* out, int n, int reset) {
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     std::lock_guard<std::mutex> lk(g_mods_mu);
@@ -567,12 +555,7 @@ int jit_prof_read(unsigned long long* out, int n, int reset) {
         buf.assign(k, 0);
         if (hipMemcpyDtoH(buf.data(), p, bytes) != hipSuccess) return -1;
         for (int i = 0; i < n && (size_t)i < k; i++) out[i] += buf[i];
-        if (reset) {
-            if (hipMemsetD8(p, 0, bytes) != hipSuccess) return -1;
-            hipDeviceptr_t q = nullptr;
-            if (hipModuleGetGlobal(&q, &bytes, m, "g_blk_dur") != hipSuccess) (void)hipGetLastError();
-            else if (q && hipMemsetD8(q, 0, bytes) != hipSuccess) return -1;
-        }
+        if (reset && hipMemsetD8(p, 0, bytes) != hipSuccess) return -1;
     }
     return any ? n : 0;
 }

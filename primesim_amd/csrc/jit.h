@@ -24,17 +24,15 @@ struct JitKernels {
     hipModule_t mod[kJitParts] = {nullptr, nullptr};
     int cc[kJitParts] = {0, 0};   // kJitRtc / kJitOffline: which compiler built each part
     hipFunction_t f[4][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
-    bool ok = false;
     std::string key;
 };
 
-bool jit_enabled();
 // The library is about to touch HIP: from now on no compiler process is started.
 void jit_note_gpu();
 std::string jit_source_tag();
 std::string jit_key(const Geo& g, int waves_1level, const std::string& arch, int part, int cc);
-// Load (compiling on a cache miss) the kernels of configuration g; leaves
-// out->ok false, after a message, when the specialisation is off or fails.
+// Load (compiling on a cache miss) the kernels of configuration g: 0, or an
+// error code with the reason (the compiler's log included) in pu_last_error().
 int jit_load(const Geo& g, JitKernels* out, bool verbose);
 // Compile into the cache without a GPU; 1 = already cached, 0 = compiled.
 int jit_warm(const Geo& g, std::string* key_out);

@@ -34,10 +34,6 @@
 #include "geo_emit.h"
 #include "jit.h"
 
-extern "C" int pu_engine_launch(const Geo* d_geo, int num_levels, char* arena, int replica0, int nblocks,
-                                const pu_req* reqs, const uint64_t* off, int32_t* delays, uint64_t* pos,
-                                uint64_t budget_ticks, uint32_t flags, int lds_headers, uint32_t* sched, int nrep,
-                                hipStream_t stream);
 extern "C" int pu_engine_lds_header_queues(void);
 extern "C" int pu_engine_init_pool(char* arena, uint64_t replica_bytes, uint64_t off_pool_free, uint64_t off_run,
                                    int pool_entries, int nreplicas, hipStream_t stream);
@@ -50,7 +46,6 @@ extern "C" int pu_engine_unit_network(const Geo* d_geo, char* base, const int32_
                                       hipStream_t s);
 extern "C" int pu_engine_init_queues(char* arena, uint64_t replica_bytes, uint64_t off_qhdr, uint64_t off_qring,
                                      int nqueues, int nreplicas, int wide, hipStream_t stream);
-extern "C" int pu_engine_occupancy(int num_levels, int mode, int* blocks_per_cu, int* lds_bytes);
 
 namespace pu {
 
@@ -295,9 +290,7 @@ struct pu_handle {
     int cus = 0;                 // compute units of the device (latency-mode launches)
     bool lds_headers_ok = false; // the replica's queue headers fit one CU's LDS
     bool lds_headers_short = false;   // latency mode for short host batches too
-    pu::JitKernels jit;          // the engine compiled for this configuration (jit.cpp), if available
-    bool jit_throughput = false; // throughput launches (headers in HBM) also run the compiled configuration
-                                 // (the default; PRIMEUNCORE_JIT_THROUGHPUT=0 keeps them ahead-of-time)
+    pu::JitKernels jit;          // the engine compiled for this configuration (jit.cpp): every launch runs it
     // ThreadSched (thread_sched.cpp): the shared one, and per-replica copies
     // made on first use of a per-replica call (pu_*_core_replica: the server's
     // sessions); the shared calls update both
@@ -345,14 +338,6 @@ struct pu_handle {
     } while (0)
 
 namespace {
-
-// the widest set of the configuration (cache levels, directory slices, TLBs)
-uint64_t max_ways(const Geo& g) {
-    uint64_t w = g.sys_type == 0 ? g.dir.nways : 0;
-    for (int l = 0; l < g.num_levels; l++) w = g.lv[l].nways > w ? g.lv[l].nways : w;
-    if (g.tlb_enable) w = g.tlb.nways > w ? g.tlb.nways : w;
-    return w;
-}
 
 int reset_state(pu_handle* h) {
     HIP_TRY(hipMemsetAsync(h->arena, 0, h->geo.replica_bytes * (size_t)h->R, h->stream), PU_EIO);
@@ -470,7 +455,7 @@ void resident_atexit() {
 }
 
 bool resident_eligible(const pu_handle* h, size_t n) {
-    return h->res.mode && h->jit.ok && h->jit.f[3][1] && h->lds_headers_ok && n <= kResCap;
+    return h->res.mode && h->jit.f[3][1] && h->lds_headers_ok && n <= kResCap;
 }
 
 // A resident kernel for `replica` is running (started or restarted here).
@@ -620,15 +605,8 @@ int launch(pu_handle* h, int replica0, int nblocks, const pu_req* d_reqs, const 
                    !(extra_flags & PU_KF_REQ16) ? 1 : 0;
     const uint32_t flags = (extra_flags & PU_KF_NOHALT) || !use_replay_mode ? extra_flags
                                                                           : (h->replay_flags | extra_flags);
-    // latency launches run the compiled configuration (one simulation alone +23%
-    // over the ahead-of-time kernel, profiles/r3i_ab_jit_single.txt); throughput
-    // launches too (+4.6% at C4 with the replica-layout offsets kept opaque,
-    // profiles/r3o_ab_opq.txt) unless PRIMEUNCORE_JIT_THROUGHPUT=0
-    const bool use_jit = h->jit.ok && (lh != 0 || h->jit_throughput);
-    int rc = use_jit ? pu::jit_launch(h->jit, d_pos != nullptr, lh != 0, nblocks, s, h->d_geo, h->arena, replica0,
-                                        d_reqs, d_off, d_delay, d_pos, budget_ticks, flags, d_sched, h->R)
-                       : pu_engine_launch(h->d_geo, h->geo.num_levels, h->arena, replica0, nblocks, d_reqs, d_off,
-                                          d_delay, d_pos, budget_ticks, flags, lh, d_sched, h->R, s);
+    int rc = pu::jit_launch(h->jit, d_pos != nullptr, lh != 0, nblocks, s, h->d_geo, h->arena, replica0, d_reqs,
+                            d_off, d_delay, d_pos, budget_ticks, flags, d_sched, h->R);
     if (rc) return pu::set_error(rc, "engine launch failed");
     HIP_TRY(hipEventRecord(h->ev1, s), PU_EIO);
     return 0;
@@ -775,9 +753,9 @@ int pu_resident_info(pu_handle* h, uint64_t* out, size_t n) {
     return (int)(n < 10 ? n : 10);
 }
 
-int pu_compiled_config(const pu_handle* h) { return h && h->jit.ok ? (h->jit_throughput ? 2 : 1) : 0; }
+int pu_compiled_config(const pu_handle* h) { return h ? 2 : 0; }
 int pu_compiled_compiler(const pu_handle* h) {
-    if (!h || !h->jit.ok) return 0;
+    if (!h) return 0;
     int off = 0;
     for (int part = 0; part < pu::kJitParts; part++) off += h->jit.cc[part] == pu::kJitOffline;
     return off == pu::kJitParts ? 2 : off == 0 ? 1 : 3;   // 3: the parts came from different compilers
@@ -885,13 +863,12 @@ pu_handle* pu_create(const pu_sim_cfg* cfg, int num_replicas, int device) {
         h->arena = nullptr;
         return fail("hipMalloc of " + std::to_string(bytes) + " bytes for the replica arena failed");
     }
-    if (pu::jit_load(geo, &h->jit, true) != 0) return fail(pu::g_err);
-    if (!h->jit.ok && max_ways(geo) > PU_MAX_WAYS)
-        return fail("sets of more than 64 ways run only in the compiled configuration (hipRTC, jit.cpp), which is "
-                    "unavailable (PRIMEUNCORE_JIT=0 or the compile failed)");
-    if (h->jit.ok) {
-        const char* e = std::getenv("PRIMEUNCORE_JIT_THROUGHPUT");
-        h->jit_throughput = max_ways(geo) > PU_MAX_WAYS || !(e && *e && std::atoi(e) == 0);
+    // the only engine kernels: a compile or load failure fails the handle (the compiler's log in the message)
+    if (const int rc = pu::jit_load(geo, &h->jit, true); rc != 0) {
+        std::string m = pu::g_err;
+        pu_destroy(h);
+        pu::set_error(rc, m);
+        return nullptr;
     }
     h->sched.stat.assign((size_t)cfg->sys.num_cores, 0);
     h->rsched.resize((size_t)num_replicas);
@@ -970,8 +947,7 @@ int pu_resident_replicas(const pu_handle* h) {
     // instantiations, each its own registers and LDS), one wave per replica
     for (int mode = 1; mode <= 2; mode++) {
         int n = 0, lds = 0;
-        int rc = h->jit.ok && h->jit_throughput ? pu::jit_occupancy(h->jit, mode, &n, &lds)
-                                                : pu_engine_occupancy(h->geo.num_levels, mode, &n, &lds);
+        int rc = pu::jit_occupancy(h->jit, mode, &n, &lds);
         if (rc) return pu::set_error(rc, "occupancy query failed");
         const int by_lds = pu::lds_limited_per_cu(lds, lds_cu, granule);
         if (by_lds > 0) n = std::min(n, by_lds);

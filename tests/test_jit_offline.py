@@ -3,7 +3,8 @@ pu_config_jit_warm writes two code objects per configuration (throughput and
 latency kernels) with hipcc when it is present, with hipRTC when the offline
 compiler is turned off (PRIMEUNCORE_JIT_HIPCC=0); the two sets have distinct
 keys (so a run prefers hipcc's), each object holds its part's kernels, and a
-second warm-up finds them cached."""
+second warm-up finds them cached.  A compile that fails returns an error with
+the compiler's log and caches nothing."""
 import ctypes as C
 import os
 import subprocess
@@ -46,3 +47,21 @@ def test_warm_up_compiles_both_parts_with_either_compiler(tmp_path):
     rtc2.mkdir()
     assert _warm(rtc2, PRIMEUNCORE_JIT_OFFLINE="0") == 0
     assert sorted(p.name for p in rtc2.glob("*.hsaco")) == fr
+
+
+FAIL_CODE = CODE.replace("print(uncore.lib().pu_config_jit_warm(C.byref(cfg)))",
+                         "rc = uncore.lib().pu_config_jit_warm(C.byref(cfg)); print(uncore.last_error()); print(rc)")
+
+
+def test_failed_compile_reports_the_log_and_caches_nothing(tmp_path):
+    """A compile that fails (hipRTC, in-process; an option that makes the
+    engine source an error) returns an error code, leaves the compiler's
+    diagnostic in pu_last_error() and writes nothing to the cache: the CPU half
+    of test_gpu_jit.py's test_failed_compile_fails_the_handle."""
+    e = dict(os.environ, PRIMEUNCORE_JIT_CACHE=str(tmp_path), PRIMEUNCORE_JIT_OFFLINE="0",
+             PRIMEUNCORE_JIT_EXTRA="-Werror=macro-redefined -DPU_JIT_PART=7")
+    r = subprocess.run([sys.executable, "-c", FAIL_CODE], env=e, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert int(r.stdout.strip().splitlines()[-1]) < 0
+    assert "'PU_JIT_PART' macro redefined" in r.stdout
+    assert list(tmp_path.iterdir()) == []

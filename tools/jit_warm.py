@@ -51,8 +51,9 @@ def configs():
 
 def live_source_tags() -> set:
     """Source tags (pu_jit_source_tag) of every engine library in the tree:
-    the product library and experiment builds (libprimeuncore_*.so).  Each is
-    asked in a child process, so their identical symbol names never meet."""
+    the product library and same-box A/B variants (libprimeuncore_*.so,
+    tools/build_variant.sh).  Each is asked in a child process, so their
+    identical symbol names never meet."""
     tags = set()
     for lib in glob.glob(os.path.join(ROOT, "primesim_amd", "libprimeuncore*.so")):
         r = subprocess.run([sys.executable, "-c", "import ctypes, sys; f = ctypes.CDLL(sys.argv[1]).pu_jit_source_tag; "
@@ -92,7 +93,7 @@ def main() -> int:
     # drop code objects of the in-tree cache compiled from sources no library in
     # the tree embeds (their name's prefix is the source tag), after an hour's
     # grace: code objects pu_create compiled on demand for user configurations
-    # and those of experiment builds stay; a cache outside the tree
+    # and those of A/B variant libraries stay; a cache outside the tree
     # (PRIMEUNCORE_JIT_CACHE) is never pruned
     intree = os.path.join(ROOT, "primesim_amd", "jit_cache")
     cache = os.environ.get("PRIMEUNCORE_JIT_CACHE") or intree

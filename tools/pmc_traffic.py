@@ -30,9 +30,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the timed (time-sliced or replica-pool, headers in HBM) launches of bench.py:
-# the compiled configuration's kernel (jit.cpp) or the ahead-of-time one
-KERNELS = ("pu_jit_uncore_s1_h0", "pu_jit_uncore_s2_h0", "uncore_kernel<1, 1, false>", "uncore_kernel<1, 2, false>")
+# the timed (time-sliced or replica-pool, headers in HBM) launches of bench.py
+KERNELS = ("pu_jit_uncore_s1_h0", "pu_jit_uncore_s2_h0")
 
 
 def run(cmd, log):
