@@ -81,6 +81,14 @@ constexpr uint32_t ST_I = 0, ST_S = 1, ST_E = 2, ST_M = 3, ST_V = 4, ST_B = 5;
 
 // Lane within the wavefront (latency-mode workgroups hold two waves).
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
+// The lane again, opaque to the compiler: what is derived from it (an LDS
+// address, a lane select) is computed at its use instead of once at the
+// kernel's start, where it would hold a VGPR across the whole request loop
+// (at 72 VGPRs those were the values that went to scratch).
+__device__ __forceinline__ int lane_here(int ln) {
+    asm volatile("" : "+v"(ln));
+    return ln;
+}
 
 __device__ __forceinline__ uint32_t rl32(uint32_t v, int l) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
@@ -1033,9 +1041,34 @@ static __shared__ uint32_t lds_dir_w[2][32];
 // branches.  The protocol code reaches it from four sites only.
 // Lane h prefetches hop h's link header and the two interval starts at its
 // ring head; only hops taking the tree branch fetch their full ring.
+//
+// The pair window (PU_PAIR_WINDOW, throughput kernels): a probe's two legs,
+// home -> p with 0 bytes and p -> home with len2 bytes, in one window.  The
+// legs are each other's reverse under X-then-Y(-then-Z) routing, and with one
+// record per undirected edge they share a link exactly when the route is a
+// straight line (one of hx, hy, hz non-zero): otherwise the forward leg leaves
+// the back leg's headers, rings and moments alone, and both legs' headers are
+// loaded, decoded and turned into M/G/1 waits by one pass, lanes [0, h) holding
+// the forward hops and [h, 2h) the back hops.  One inclusive scan serves both
+// (the back leg's offsets are S(l) - S(h-1): the scan term holds no packet
+// length and no tree shift), the hop loop runs once per leg (one body, a
+// rolled loop), and one write-back and one statistics add cover both.  Taken
+// when `pair` comes in true, src != dst, 2h <= 64 and the route is no straight
+// line; `pair` returns whether it was.  The back leg starts at base_t +
+// (tpre + forward delay), the sum in parentheses an int as the caller's running
+// delay is (tpre: that delay with what happens at p already added, evaluated
+// by the caller beforehand), exactly as two calls would have it, and the two
+// legs' delays are returned as one sum.
+#ifndef PU_PAIR_WINDOW
+#define PU_PAIR_WINDOW 1
+#endif
+template <bool LH, bool WIDE>
+constexpr bool pair_window() { return PU_PAIR_WINDOW && !LH && !WIDE; }
 template <bool LH, int NL, bool WIDE>
 __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char* base_in, int src, int dst, int len,
-                                                 uint64_t timer, uint32_t& hq_head) {
+                                                 uint64_t timer, uint32_t& hq_head, bool& pair, int len2,
+                                                 int64_t base_t, int tpre) {
+    constexpr bool PW = pair_window<LH, WIDE>();
     PROF_T(p_pre);
     NetCtx c;
     AS1 char* base = (AS1 char*)(char*)uni64((uint64_t)base_in);
@@ -1060,7 +1093,10 @@ __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char
     dst = (int)uni32((uint32_t)dst);
     len = (int)uni32((uint32_t)len);
     timer = uni64(timer);
-    if (src == dst) return 0;
+    if (src == dst) {
+        pair = false;
+        return 0;
+    }
     const int ln = lane_id();
     // network.cpp:104 packet length; the engine only sends 0-byte and block
     // messages (the packed header counts those two lengths; the unit hook's
@@ -1080,22 +1116,42 @@ __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char
     net_coords(c, dst, rx, ry, rz);
     const int hx = abs(rx - sx), hy = abs(ry - sy), hz = abs(rz - sz);
     const int hops = hx + hy + hz;
+    // the pair window: both legs in 64 lanes, and no link of one leg in the other
+    bool pw = false;
+    if constexpr (PW) {
+        pw = pair && 2 * hops <= 64 && (hx != 0) + (hy != 0) + (hz != 0) >= 2;
+        len2 = (int)uni32((uint32_t)len2);
+        if (pw && len2 != 0 && len2 != c.blk_len) err |= PU_ERRF_QUEUE;
+    }
+    pair = pw;
+    // the back leg's packet length (derived where it is used: no register held for it)
+    const auto plen2 = [&]() { return len2 == 0 ? c.header_flits : c.plen_blk; };
+    const int thops = pw ? 2 * hops : hops;   // hops of all legs
     uint64_t t = timer + c.inject;
     uint64_t mg1 = 0;
     PROF_ADD(PF_NPRE, p_pre);
-    for (int b0 = 0; b0 < hops; b0 += 64) {
+    for (int b0 = 0; b0 < thops; b0 += 64) {
         PROF_T(p_setup);
         PROF_CNT(PF_WINDOWS, 1);
         // ---- prefetch the window: lane h = hop b0+h loads its link's header
         // (32 B: visit counts, ring cursor, newest finish, the first interval start)
         const int h = b0 + ln;
-        const int nh = hops - b0 < 64 ? hops - b0 : 64;
+        const int nh = thops - b0 < 64 ? thops - b0 : 64;
         // Every lane loads: a lane past the route takes the route's last hop,
         // the same address as that hop's own lane (no extra line, no
         // exec-masked branch, no zeroed registers); such lanes are masked
         // wherever a hop's results are used (ln < nh), and their copy of a
         // real header raises no error that hop does not raise itself.
-        const int rq = net_route_link(c, h < hops ? h : hops - 1, sx, sy, sz, rx, ry, rz, hx, hy);
+        int rq;
+        if (PW && pw) {
+            // lanes [hops, 2 hops): the route back, dst -> src (a pair window is one window: b0 = 0)
+            const int hh = h < thops ? h : thops - 1;
+            const bool bk = hh >= hops;
+            rq = net_route_link(c, bk ? hh - hops : hh, bk ? rx : sx, bk ? ry : sy, bk ? rz : sz, bk ? sx : rx,
+                                bk ? sy : ry, bk ? sz : rz, hx, hy);
+        } else {
+            rq = net_route_link(c, h < hops ? h : hops - 1, sx, sy, sz, rx, ry, rz, hx, hy);
+        }
         v4u32 ha, hb, hc;
         hdr_load<LH, WIDE>(c, rq, ha, hb, hc);
         uint64_t vcache = PU_MG1_CACHE_NONE;
@@ -1144,9 +1200,20 @@ __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char
         // LB_j + p cannot take the M/G/1 branch, so its full ring is certainly
         // needed: stage those rings now, ring_pf<LH>() ahead, in hop order.
         // (every lane computes; the mask drops the lanes past the route)
-        const uint64_t nhm = nh >= 64 ? ~0ull : ((1ull << nh) - 1);
-        const uint64_t lb = t + (uint64_t)(ln + 1) * c.router + (uint64_t)ln * c.link_delay;
-        const uint64_t M = ballot(vfront <= lb + (uint64_t)plen) & nhm;
+        // A pair window runs everything from here to the write-back once per
+        // leg (`leg`, one rolled loop): lanes [l0, l1) with the leg's packet
+        // length, the back leg's prediction mask from its true start time.
+        // Every ring a leg staged was consumed by that leg (predicted hops are
+        // tree hops), so the staging cursors start afresh.
+        uint64_t X = 0;                 // exclusive scan of the hops' assumed delays
+        const int nleg = PW && pw ? 2 : 1;
+#pragma clang loop unroll(disable)
+        for (int leg = 0; leg < nleg; leg++) {
+        const int l0 = PW && leg ? hops : 0, l1 = PW && pw ? l0 + hops : nh;
+        const int pl = PW && leg ? plen2() : plen;
+        const uint64_t nhm = (l1 >= 64 ? ~0ull : ((1ull << l1) - 1)) & (~0ull << l0);
+        const uint64_t lb = t + (uint64_t)(ln - l0 + 1) * c.router + (uint64_t)(ln - l0) * c.link_delay;
+        const uint64_t M = ballot(vfront <= lb + (uint64_t)pl) & nhm;
         uint64_t mi = M, mc = M;        // issue / consume cursors over the predicted hops
         int issued = 0, consumed = 0;
         constexpr int RPF = ring_pf<LH>();
@@ -1171,16 +1238,24 @@ __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char
         // operation at 96 VGPRs and had it rescan after each tree hop; with
         // the 32-B headers that kernel spills no VGPR, and the shift is +0.5%
         // on the C4 headline, same box: profiles/r5c_ab_ens.txt.)
-        uint64_t S = 0, A0 = 0, sh = 0;
-        const uint64_t t0 = t;
-        {
+        // Only the exclusive sums X = S - e stay in registers: hop j arrives at
+        // t0 + router + X(j) + sh, and the inclusive sum at a leg's last hop is
+        // X + e of that lane.
+        uint64_t sh = 0;
+        uint64_t t0 = t;
+        if (!PW || leg == 0) {
             // lanes past the route add their copies' terms above it: an
-            // inclusive scan never carries them down
+            // inclusive scan never carries them down.  One scan serves both
+            // legs of a pair window: the back leg's offsets are S(l) - S(hops-1)
+            // = X(l) - X(hops) (the term holds no packet length, and the shifts
+            // stay outside it)
             const uint64_t e = vd + c.link_delay + c.router;
-            S = ballot(e >= (1ull << 26)) == 0 ? (uint64_t)scan_incl_u32((uint32_t)e) : scan_incl_u64(e);
-            A0 = t + c.router + (S - e);
+            const uint64_t S = ballot(e >= (1ull << 26)) == 0 ? (uint64_t)scan_incl_u32((uint32_t)e) : scan_incl_u64(e);
+            X = S - e;
+        } else {
+            t0 -= rl64(X, hops);        // 2 hops <= 64: lane `hops` is the back leg's first
         }
-        int js = 0;
+        int js = l0;
         {
             // the window's live hops and the M/G/1 hops' finish times as wave
             // masks (one v_cndmask per dword), the staging slots as wrapping
@@ -1191,17 +1266,17 @@ __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char
             // scalar unit, ran 9% slower closed loop: more scalar
             // instructions than it saved)
             int islot = issued % RPF, cslot = 0;
-            while (js < nh) {
+            while (js < l1) {
                 const uint64_t live = nhm & (~0ull << js);
-                const uint64_t A = A0 + sh;
-                const uint64_t cand = ballot(vfront <= A + (uint64_t)plen) & live;
-                const int jt = cand ? (int)__builtin_ctzll(cand) : nh;
+                const uint64_t A = X + (t0 + c.router + sh);
+                const uint64_t cand = ballot(vfront <= A + (uint64_t)pl) & live;
+                const int jt = cand ? (int)__builtin_ctzll(cand) : l1;
                 // hops [js, jt) took M/G/1: their finish times
                 const uint64_t fm = jt >= 64 ? live : live & ((1ull << jt) - 1);
-                vfin = selm64(fm, vfin, A + vd + (uint64_t)plen);
+                vfin = selm64(fm, vfin, A + vd + (uint64_t)pl);
                 mg1 += (uint64_t)(jt - js);
-                if (jt == nh) {                               // the rest of the window is M/G/1
-                    t = t0 + rl64(S, nh - 1) + sh;
+                if (jt == l1) {                               // the rest of the leg is M/G/1
+                    t = t0 + rl64(X, l1 - 1) + rl64(vd, l1 - 1) + c.link_delay + c.router + sh;
                     break;
                 }
                 PROF_T(p_tree);
@@ -1236,7 +1311,7 @@ __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the ring's LDS read, in this region
 #endif
                 PROF_ADD(PF_T_LDS, p_pick);         // hop pick, DMA wait (NWAIT), ring from LDS
-                d = tree_op<LH>(c, q, v, head, cnt, tj, (uint64_t)plen, c.link_delay, err, f0n, f1n, tslot);
+                d = tree_op<LH>(c, q, v, head, cnt, tj, (uint64_t)pl, c.link_delay, err, f0n, f1n, tslot);
                 PROF_T(p_upd);
                 if (cnt >= PU_QMAX) {               // the next call's prune (history_tree.cpp:49-55), done now
                     head = (head + 1) & (PU_QRING - 1);
@@ -1255,14 +1330,26 @@ __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char
                 sh += d - rl64(vd, jt);
                 // (hop jt's assumed wait vd is not read again: later M/G/1 finish
                 // times and shifts use the lanes after it)
-                wl_hop(vhead, head, vcnt, cnt, vf0, f0n, vfin, tj + d + (uint64_t)plen, jt);
+                wl_hop(vhead, head, vcnt, cnt, vf0, f0n, vfin, tj + d + (uint64_t)pl, jt);
                 t = tj + d + c.link_delay;
                 js = jt + 1;
                 PROF_ADD(PF_T_UPD, p_upd);          // prune, refill (T_REFILL), hop results into the window
                 PROF_ADD(PF_NTREE, p_tree);
             }
         }
+        if (PW && pw && leg == 0) {
+            // the forward leg is done (network.cpp:146-156) and the back leg
+            // starts; `timer` becomes that start less the forward delay, so
+            // that the end time less `timer` is the two delays' sum
+            t += c.router;
+            t += (uint64_t)(plen - 1);
+            const uint64_t dfwd = t - timer;
+            const uint64_t start = (uint64_t)(base_t + (tpre + (int)dfwd));
+            timer = start - dfwd;
+            t = start + c.inject;
+        }
         PROF_ADD(PF_NHOPS, p_hops);
+        }   // leg
         PROF_T(p_wb);
         // ---- header write-back, one hop per lane (queue_model_m_g_1.cpp:45-55)
         if (ln < nh) {
@@ -1276,7 +1363,8 @@ __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char
                 st.n = st.n + 1.0;
             } else {
                 st.n = st.n + 1.0;
-                if (plen != (int)c.p0) st.sum1 = st.sum1 + 1.0;
+                // each lane's own packet length (a pair window's back leg: plen2)
+                if ((PW && pw && ln >= hops ? plen2() : plen) != (int)c.p0) st.sum1 = st.sum1 + 1.0;
             }
             st.newest = vfin > st.newest ? vfin : st.newest;
             q_store_hdr<LH, WIDE>(c, rq, st, vhead != hs.head || vcnt != hs.count || vf0 != hs.f0);
@@ -1296,17 +1384,19 @@ __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char
     }
     PROF_T(p_post);
     t += c.router;
-    t += (uint64_t)(plen - 1);
-    const uint64_t dist = (uint64_t)hops;
+    t += (uint64_t)((PW && pw ? plen2() : plen) - 1);
+    // a pair window adds both transmits' sums at once
+    const uint64_t dist = (uint64_t)thops;
     {   // the six network sums in one ds_add_u64, lane k adding sum k (written
         // into the lanes by v_writelane: no lane compares)
-        const uint64_t tot = t - timer, fl = dist * (uint64_t)plen;
+        const uint32_t plsum = (uint32_t)(PW && pw ? plen + plen2() : plen);
+        const uint64_t tot = t - timer, fl = (uint64_t)hops * (uint64_t)plsum;
         uint32_t lo = 0, hi = 0;
-        lo = wlane<SN_ACC>(lo, 1u);
+        lo = wlane<SN_ACC>(lo, PW && pw ? 2u : 1u);
         lo = wlane<SN_DIST>(lo, (uint32_t)dist);
         lo = wlane<SN_TOTAL>(lo, (uint32_t)tot);
         hi = wlane<SN_TOTAL>(hi, (uint32_t)(tot >> 32));
-        lo = wlane<SN_PLEN>(lo, (uint32_t)plen);
+        lo = wlane<SN_PLEN>(lo, plsum);
         lo = wlane<SN_FLITS>(lo, (uint32_t)fl);
         // mg1 <= hops < 2^9 (at most 65,536 nodes): no high word; flits =
         // hops x plen has none either while the packed header's two packet
@@ -1477,7 +1567,18 @@ struct Engine {
     }
     __device__ __forceinline__ uint64_t transmit(int src, int dst, int len, uint64_t timer) {
         PROF_T(p0);
-        uint64_t d = net_transmit<LH, NL, WIDE>(g, base, src, dst, len, timer, hq_head);
+        bool pair = false;
+        uint64_t d = net_transmit<LH, NL, WIDE>(g, base, src, dst, len, timer, hq_head, pair, 0, 0, 0);
+        PROF_ADD(PF_NET, p0);
+        return d;
+    }
+    // A probe's leg: with `pair` true, both legs in one window when the route
+    // allows it (net_transmit's pair window; `pair` returns whether it did,
+    // and the delay is then both legs').
+    __device__ __forceinline__ uint64_t transmit_leg(int src, int dst, int len, uint64_t timer, bool& pair, int len2,
+                                                     int64_t base_t, int tpre) {
+        PROF_T(p0);
+        uint64_t d = net_transmit<LH, NL, WIDE>(g, base, src, dst, len, timer, hq_head, pair, len2, base_t, tpre);
         PROF_ADD(PF_NET, p0);
         return d;
     }
@@ -1543,7 +1644,7 @@ struct Engine {
                 invalid = true;
                 way = (int)__builtin_ctzll(inv);
             } else {
-                way = lru_way(v.mts, (uint64_t)ln < nways ? ln : 64, nways);
+                way = lru_way(v.mts, (uint64_t)ln < nways ? lane_here(ln) : 64, nways);
             }
         } else {
             // first invalid way over the chunks, else the (timestamp, way)
@@ -1872,10 +1973,34 @@ struct Engine {
             k++;
             int t = pipe;
             // home -> p, share/inval below p, p -> home: one transmit site
+            if constexpr (pair_window<LH, WIDE>()) {
+                // What happens at p first: it commutes with the forward leg.  down
+                // takes no time argument; at every level (down_impl<LV> for LV =
+                // NL-1 .. 0, through children<LV>) it reads the cache's alive
+                // word and the set of r.addr, sets that line's state, counts
+                // SN_LOCKDOWN, and returns sums and maxima of the levels'
+                // access_time constants.  A transmit reads and writes link
+                // headers and rings and its own six network sums only.  So the
+                // delay and every stored byte are the same in either order,
+                // and with the delay in hand both legs can share one window.
+                // The sums are those of t = pipe; t += d_fwd; t += d_down; back
+                // leg at base_t + t; t += d_back: int additions wrap, so adding
+                // d_down first gives the same t at every later point.
+                const uint64_t start = (uint64_t)(base_t + t);
+                t += inval ? down<last, true>(p, r) : down<last, false>(p, r);
 #pragma clang loop unroll(disable)
-            for (int back = 0; back < 2; back++) {
-                t += (int)transmit(back ? p : home, back ? home : p, back ? reply_len : 0, (uint64_t)(base_t + t));
-                if (!back) t += inval ? down<last, true>(p, r) : down<last, false>(p, r);
+                for (int back = 0; back < 2; back++) {
+                    bool paired = !back;
+                    t += (int)transmit_leg(back ? p : home, back ? home : p, back ? reply_len : 0,
+                                           back ? (uint64_t)(base_t + t) : start, paired, reply_len, base_t, t);
+                    if (paired) break;   // both legs ran in one window: the delay was their sum
+                }
+            } else {
+#pragma clang loop unroll(disable)
+                for (int back = 0; back < 2; back++) {
+                    t += (int)transmit(back ? p : home, back ? home : p, back ? reply_len : 0, (uint64_t)(base_t + t));
+                    if (!back) t += inval ? down<last, true>(p, r) : down<last, false>(p, r);
+                }
             }
             if (single) return t;
             mx = t > mx ? t : mx;
@@ -1944,7 +2069,8 @@ struct Engine {
             const v4u32 a = lds_dir_a[ln];
             m.tag = u64of(a.x, a.y);
             m.ts = (int64_t)u64of(a.z, a.w);
-            m.w = u64of(lds_dir_w[0][ln], lds_dir_w[1][ln]);
+            const int lw = lane_here(ln);
+            m.w = u64of(lds_dir_w[0][lw], lds_dir_w[1][lw]);
         } else if (mine) {
             m = lines[line0 + (uint64_t)ln];
         } else {
@@ -2529,7 +2655,7 @@ __device__ __forceinline__ void stats_init() {
     const int ln = lane_id();
     if (ln < SN_COUNT) lds_stat[ln] = 0;
     if constexpr (kAliveLds)
-        for (int i = ln; i < kAliveWords; i += 64) lds_alive[i] = 0u;
+        for (int i = lane_here(ln); i < kAliveWords; i += 64) lds_alive[i] = 0u;
 #ifdef PU_PROF
     if (ln < PF_COUNT) lds_prof[ln] = 0;
 #endif

@@ -1,6 +1,6 @@
 """Warm the compile-time-configuration cache (primesim_amd/jit_cache/) for every
 configuration the GPU tests, smoke() and bench.py use: the golden XMLs, the
-C1-C5 presets, the DRAM-bank test geometries and tests/extra_configs.py.  Runs on the CPU (hipcc, in a
+C1-C5 presets, the DRAM-bank test geometries, tests/extra_configs.py and tests/pair_window_cases.py.  Runs on the CPU (hipcc, in a
 child process of each worker; no GPU), several compiles at once; a configuration already cached is skipped.
 A same-box A/B of compile options (tools/gpu_session.sh V@FLAGS) compiles its variant with hipRTC on the
 GPU box unless the variant is warmed here first with the same environment:
@@ -44,6 +44,11 @@ def configs():
     try:
         from extra_configs import extra_configs
         out.extend(extra_configs())
+    except ImportError:
+        pass
+    try:
+        from pair_window_cases import pair_window_configs
+        out.extend(pair_window_configs())
     except ImportError:
         pass
     return out

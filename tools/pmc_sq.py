@@ -39,6 +39,7 @@ def main() -> None:
     ap.add_argument("--out", required=True)
     ap.add_argument("--work", default=os.path.join(ROOT, "gpurun_out", "pmc_sq"))
     ap.add_argument("--kernel", default=KERNEL, help="kernel name substrings to sum over, '|'-separated")
+    ap.add_argument("--passes", default="", help="comma-separated indices into PASSES to run (default: all)")
     ap.add_argument("bench_args", nargs=argparse.REMAINDER)
     a = ap.parse_args()
     bargs = [x for x in a.bench_args if x != "--"]
@@ -46,9 +47,14 @@ def main() -> None:
     os.makedirs(a.work, exist_ok=True)
     os.environ.setdefault("TMPDIR", "/tmp")
     out = {"bench_args": bargs, "passes": PASSES, "per_launch": {}}
+    only = {int(x) for x in a.passes.split(",") if x != ""}
     for i, counters in enumerate(PASSES):
         d = os.path.join(a.work, f"p{i}")
         shutil.rmtree(d, ignore_errors=True)
+        if os.path.exists(os.path.join(a.work, f"p{i}.log")):
+            os.remove(os.path.join(a.work, f"p{i}.log"))
+        if only and i not in only:
+            continue
         cmd = ["rocprofv3", "--pmc", *counters, "--output-format", "csv", "-d", d, "-o", "run", "--",
                sys.executable, os.path.join(ROOT, "bench.py"), *bargs]
         print("+", " ".join(cmd), flush=True)

@@ -102,7 +102,7 @@ def marker_lines() -> dict:
                 return k + 1
         raise SystemExit(f"marker not found: {pat}")
     nt = find("__device__ __forceinline__ uint64_t net_transmit(")
-    win0 = find("for (int b0 = 0; b0 < hops; b0 += 64)", nt)
+    win0 = find("for (int b0 = 0; b0 < thops; b0 += 64)", nt)
     post = find("PROF_T(p_post);", win0)
     trees = []
     k = win0
