@@ -273,6 +273,13 @@ long pu_config_geo_source(const pu_sim_cfg* cfg, char* buf, size_t cap);
 int pu_config_jit_warm(const pu_sim_cfg* cfg);
 int pu_compiled_config(const pu_handle* h);
 int pu_compiled_compiler(const pu_handle* h);
+/* The symbol name of the engine kernel handle h launched last, for example
+ * "pu_jit_uncore_s1_h0" (s: 0 fixed ranges, 1 time-sliced, 2 replica pool,
+ * 3 resident; h: queue headers in HBM 0 or in LDS 1); a command handed to a
+ * running resident kernel counts as a launch of it.  "" before any launch and
+ * for NULL.  Read-only and free (the handle remembers an index): tests use it
+ * to prove which kernel a call reached.  No reference counterpart. */
+const char* pu_last_launch_kernel(pu_handle* h);
 /* The 8-hex-digit tag of the engine sources this library compiles: the prefix
  * of every code object it writes to the cache (cache maintenance keeps the
  * code objects whose prefix some library still carries). */

@@ -346,6 +346,16 @@ std::string jit_source_tag() {
 
 void jit_note_gpu() { g_gpu_used = true; }
 
+// The one table of the engine kernels' symbol names (engine.hip PU_JIT_KERNEL):
+// load_module finds them by it, pu_last_launch_kernel reports from it.
+const char* jit_kernel_name(int s, int h) {
+    static const char* const names[4][2] = {{"pu_jit_uncore_s0_h0", "pu_jit_uncore_s0_h1"},
+                                            {"pu_jit_uncore_s1_h0", "pu_jit_uncore_s1_h1"},
+                                            {"pu_jit_uncore_s2_h0", nullptr},
+                                            {nullptr, "pu_jit_uncore_s3_h1"}};
+    return s >= 0 && s < 4 && h >= 0 && h < 2 ? names[s][h] : nullptr;
+}
+
 std::string jit_key(const Geo& g, int waves_1level, const std::string& arch, int part, int cc) {
     uint64_t h = fnv1a("primeuncore-jit-2");
     for (int i = 0; i < pu_jit_nsrc; i++) {
@@ -400,16 +410,14 @@ bool load_module(const std::vector<char>& code, int part, JitKernels* out, std::
         *why = "the device refused the code object";
         return false;
     }
-    static const char* names[4][2] = {{"pu_jit_uncore_s0_h0", "pu_jit_uncore_s0_h1"},
-                                      {"pu_jit_uncore_s1_h0", "pu_jit_uncore_s1_h1"},
-                                      {"pu_jit_uncore_s2_h0", nullptr},
-                                      {nullptr, "pu_jit_uncore_s3_h1"}};
-    for (int s = 0; s < 4; s++)
-        if (names[s][part] && hipModuleGetFunction(&out->f[s][part], mod, names[s][part]) != hipSuccess) {
+    for (int s = 0; s < 4; s++) {
+        const char* name = jit_kernel_name(s, part);
+        if (name && hipModuleGetFunction(&out->f[s][part], mod, name) != hipSuccess) {
             (void)hipModuleUnload(mod);
-            *why = std::string("the code object lacks ") + names[s][part];
+            *why = std::string("the code object lacks ") + name;
             return false;
         }
+    }
     out->mod[part] = mod;
     std::lock_guard<std::mutex> lk(g_mods_mu);
     g_mods.push_back(mod);
@@ -566,7 +574,8 @@ int jit_launch(const JitKernels& k, bool sliced, bool lds_headers, int nblocks, 
     void* args[] = {(void*)&d_geo, (void*)&arena, (void*)&replica0, (void*)&reqs, (void*)&off,
                     (void*)&delays, (void*)&pos, (void*)&budget_ticks, (void*)&flags, (void*)&sched, (void*)&nrep};
     // latency mode (headers in LDS): two waves, the second the M/G/1 helper (engine.hip)
-    hipFunction_t f = sched ? k.f[2][0] : k.f[sliced ? 1 : 0][lds_headers ? 1 : 0];
+    const int id = jit_launch_kernel(sliced, lds_headers, sched != nullptr);
+    hipFunction_t f = k.f[id >> 1][id & 1];
     hipError_t e = hipModuleLaunchKernel(f, (unsigned)nblocks, 1, 1,
                                          lds_headers ? 128 : 64, 1, 1, 0, stream, args, nullptr);
     return e == hipSuccess ? 0 : PU_EIO;

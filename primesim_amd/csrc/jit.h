@@ -38,6 +38,16 @@ int jit_load(const Geo& g, JitKernels* out, bool verbose);
 int jit_warm(const Geo& g, std::string* key_out);
 void jit_unload(JitKernels* k);
 int jit_prof_read(unsigned long long* out, int n, int reset);
+// The symbol name of kernel f[s][h] (the one table of them), nullptr where
+// there is no such kernel.
+const char* jit_kernel_name(int s, int h);
+// Which kernel a jit_launch with these arguments runs, as the index s * 2 + h
+// of f[s][h]: the replica pool when a scheduling array is given (headers in
+// HBM), else the time-sliced or the fixed-range shape.
+inline int jit_launch_kernel(bool sliced, bool lds_headers, bool pool) {
+    return pool ? 2 * 2 : (sliced ? 1 : 0) * 2 + (lds_headers ? 1 : 0);
+}
+constexpr int kJitResidentKernel = 3 * 2 + 1;   // the same index for what jit_launch_resident runs
 int jit_launch(const JitKernels& k, bool sliced, bool lds_headers, int nblocks, hipStream_t stream, const Geo* d_geo,
                char* arena, int replica0, const pu_req* reqs, const uint64_t* off, int32_t* delays, uint64_t* pos,
                uint64_t budget_ticks, uint32_t flags, uint32_t* sched = nullptr, int nrep = 0);

@@ -291,6 +291,7 @@ struct pu_handle {
     bool lds_headers_ok = false; // the replica's queue headers fit one CU's LDS
     bool lds_headers_short = false;   // latency mode for short host batches too
     pu::JitKernels jit;          // the engine compiled for this configuration (jit.cpp): every launch runs it
+    int last_kernel = -1;        // jit.f[s][h] of the last launch or resident command, as s * 2 + h (-1: none yet)
     // ThreadSched (thread_sched.cpp): the shared one, and per-replica copies
     // made on first use of a per-replica call (pu_*_core_replica: the server's
     // sessions); the shared calls update both
@@ -496,6 +497,7 @@ int resident_ensure(pu_handle* h, int replica) {
     if (pu::jit_launch_resident(h->jit, R.stream, h->d_geo, h->arena, replica, R.stage, R.mb_dev, R.idle_ticks,
                                 (int)kResCap) != 0)
         return pu::set_error(PU_EIO, "resident kernel launch failed");
+    h->last_kernel = pu::kJitResidentKernel;
     R.running = true;
     R.replica = replica;
     R.launches++;
@@ -519,6 +521,7 @@ int resident_run(pu_handle* h, int replica, const pu_req* reqs, size_t n, uint32
     std::atomic_thread_fence(std::memory_order_release);
     const uint64_t seq = ++R.seq;
     mb->h.seq = seq;
+    h->last_kernel = pu::kJitResidentKernel;   // the command goes to the running resident kernel
     // a one-request command may come back as the fast word {seq, delay}
     bool fast = false;
     for (uint64_t spin = 1;; spin++) {
@@ -608,6 +611,7 @@ int launch(pu_handle* h, int replica0, int nblocks, const pu_req* d_reqs, const 
     int rc = pu::jit_launch(h->jit, d_pos != nullptr, lh != 0, nblocks, s, h->d_geo, h->arena, replica0, d_reqs,
                             d_off, d_delay, d_pos, budget_ticks, flags, d_sched, h->R);
     if (rc) return pu::set_error(rc, "engine launch failed");
+    h->last_kernel = pu::jit_launch_kernel(d_pos != nullptr, lh != 0, d_sched != nullptr);   // what jit_launch ran
     HIP_TRY(hipEventRecord(h->ev1, s), PU_EIO);
     return 0;
 }
@@ -759,6 +763,13 @@ int pu_compiled_compiler(const pu_handle* h) {
     int off = 0;
     for (int part = 0; part < pu::kJitParts; part++) off += h->jit.cc[part] == pu::kJitOffline;
     return off == pu::kJitParts ? 2 : off == 0 ? 1 : 3;   // 3: the parts came from different compilers
+}
+
+const char* pu_last_launch_kernel(pu_handle* h) {
+    if (!h) return "";
+    std::lock_guard<std::mutex> lk(h->mu);
+    const char* name = h->last_kernel < 0 ? nullptr : pu::jit_kernel_name(h->last_kernel >> 1, h->last_kernel & 1);
+    return name ? name : "";
 }
 
 const char* pu_jit_source_tag(void) {

@@ -59,6 +59,7 @@ def lib() -> C.CDLL:
         "pu_config_jit_warm": (C.c_int, [P(A.SimCfg)]),
         "pu_compiled_config": (C.c_int, [C.c_void_p]),
         "pu_compiled_compiler": (C.c_int, [C.c_void_p]),
+        "pu_last_launch_kernel": (C.c_char_p, [C.c_void_p]),
         "pu_jit_source_tag": (C.c_char_p, []),
         "pu_jit_prof_read": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int, C.c_int]),
         "pu_destroy": (None, [C.c_void_p]),
@@ -530,6 +531,11 @@ class UncoreManager:
 
     def last_kernel_ms(self) -> float:
         return float(lib().pu_last_kernel_ms(self._handle()))
+
+    def last_launch_kernel(self) -> str:
+        """Symbol name of the engine kernel the handle launched last
+        (pu_last_launch_kernel), "" before any launch."""
+        return lib().pu_last_launch_kernel(self._handle()).decode()
 
     def set_resident(self, mode: int) -> int:
         """Resident mode for uncore_access / short batches (pu_set_resident):

@@ -29,6 +29,18 @@ def test_exports_every_declared_symbol():
     assert not missing, missing
 
 
+def test_mirror_declares_every_handle_query():
+    """The ctypes mirror gives the read-only handle queries their C types (a
+    char* result left at the default int would be truncated), and they answer
+    for no handle without touching a device."""
+    L = lib()
+    assert "pu_last_launch_kernel" in declared_symbols()
+    assert L.pu_last_launch_kernel.restype is C.c_char_p
+    assert list(L.pu_last_launch_kernel.argtypes) == [C.c_void_p]
+    assert L.pu_last_launch_kernel(None) == b""          # no handle: nothing was launched
+    assert L.pu_compiled_config(None) == 0 and L.pu_compiled_compiler(None) == 0
+
+
 def test_version_and_error_strings():
     assert b"gfx950" in lib().pu_version()
     assert isinstance(P.uncore.last_error(), str)

@@ -14,19 +14,27 @@ from golden_util import Case, assert_stats_match, big_case_names, case_names
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("name", case_names() + big_case_names())
-def test_engine_reproduces_reference(name):
+def _reproduces_reference(name, resident=None, kernel=None):
+    """The golden through access_batch on one replica; `resident` sets the
+    resident mode first, `kernel` is the engine kernel every call must have
+    launched (pu_last_launch_kernel)."""
     c = Case(name)
     um = P.UncoreManager()
     um.init(P.load_config(c.xml_path), replicas=1)
     try:
+        if resident is not None:
+            um.set_resident(resident)
         if c.closed:
             um.set_replay_mode(P.uncore.PU_REPLAY_CLOSED)
         for prog, th in c.threads:
             um.allocCore(prog, th)
         # large runs go in chunks (the open message's delay carries across calls)
         step = 200_000
-        d = np.concatenate([um.access_batch(c.reqs[a:a + step]) for a in range(0, len(c.reqs), step)])
+        parts = []
+        for a in range(0, len(c.reqs), step):
+            parts.append(um.access_batch(c.reqs[a:a + step]))
+            assert kernel is None or um.last_launch_kernel() == kernel
+        d = np.concatenate(parts)
         c.check_delays(d)
         np.testing.assert_array_equal(um.completion(), c.completion)
         st = um.stats().as_dict()
@@ -39,6 +47,11 @@ def test_engine_reproduces_reference(name):
         um.close()
 
 
+@pytest.mark.parametrize("name", case_names() + big_case_names())
+def test_engine_reproduces_reference(name):
+    _reproduces_reference(name)
+
+
 @pytest.mark.parametrize("name", ["c1_hot", "c4_allcores", "three_level", "l2_shared_bus", "c5_prodcons_256",
                                   "c4_closed"])
 @pytest.mark.parametrize("mode", ["0", "2"])
@@ -47,7 +60,13 @@ def test_engine_header_modes(name, mode, monkeypatch):
     headers in HBM for every launch (the throughput kernel's path, which the
     bench runs); "2" uses the latency mode (headers in LDS, launches of at most
     one replica per CU) for short host batches too, which otherwise run with
-    the headers in HBM."""
+    the headers in HBM.  Resident mode would take a short batch before either
+    launch (access_batch), so mode "2" turns it off; with the headers kept out
+    of LDS (mode "0") it is not eligible.  The handle names the kernel of every
+    launch: the placement asked for is the one that ran."""
     monkeypatch.setenv("PRIMEUNCORE_LDS_HEADERS", mode)
-    test_engine_reproduces_reference(name)
+    if mode == "0":
+        _reproduces_reference(name, kernel="pu_jit_uncore_s0_h0")
+    else:
+        _reproduces_reference(name, resident=0, kernel="pu_jit_uncore_s0_h1")
 

@@ -28,22 +28,18 @@ def test_handle_reports_its_variant():
     _reports_compiled_configuration("c1_hot")
 
 
-# The two tests below date from when the library held a second set of engine
+# The test below dates from when the library held a second set of engine
 # kernels that read the geometry at run time, selected by environment
-# variables that are gone with them.  The cases are retired in steps, the rest
-# with the next change to this file; until then each checks that a handle on
-# its kind of configuration (one and three levels, bus system, TLB, limited
-# pointer, 3-D mesh, closed loop) reports the compiled configuration, and
-# re-runs its golden.
+# variables that are gone with them.  Its cases are retired in steps (its
+# companion, test_ahead_of_time_kernels_match_reference, went when
+# test_gpu_kernel_matrix.py began to run every golden on every kernel, each
+# cell also checking that the handle reports the compiled configuration);
+# these five go with the next change to this file.  Until then each checks
+# that a handle on its kind of configuration (one level, multi-program, bus
+# system, TLB, closed loop) reports the compiled configuration, and re-runs
+# its golden.
 @pytest.mark.parametrize("name", ["c1_hot", "c3_multiprog", "bus_c2", "tlb_c3", "c4_closed"])
 def test_ahead_of_time_throughput_launches_match_reference(name):
-    _reports_compiled_configuration(name)
-    test_engine_reproduces_reference(name)
-
-
-@pytest.mark.parametrize("name", ["c1_hot", "c3_multiprog", "three_level", "bus_c2", "tlb_c3", "limited_ptr", "mesh3d",
-                                  "c4_closed"])
-def test_ahead_of_time_kernels_match_reference(name):
     _reports_compiled_configuration(name)
     test_engine_reproduces_reference(name)
 
