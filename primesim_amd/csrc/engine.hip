@@ -63,10 +63,37 @@ namespace {
 // (opaque: 4; the latency kernel, with registers to spare, keeps them
 // folded): +4.6% on the C4 headline against the same kernel reading a
 // run-time Geo, same box (profiles/r3o_ab_opq.txt).
+//
+// PU_OFF32 (throughput kernels, on by default; -DPU_OFF32=0 restores the
+// 64-bit path): a replica's arena is far smaller than 4 GiB, so an address
+// into it is the wave-uniform 64-bit replica base plus a 32-bit byte offset,
+// layout constant + index x element size in 32-bit arithmetic (Arr below),
+// which the hardware adds itself (global_* vOFF, s[base:base+1]).  The opaque
+// offset is then one scalar move of a literal: no high word, no 64-bit add
+// chain per address.  Taken only when the compiled geometry's replica_bytes
+// fits 32 bits (every array of a replica, hence every offset + index x size,
+// lies below it); a larger configuration silently keeps the 64-bit path.
+#ifndef PU_OFF32
+#define PU_OFF32 1
+#endif
+template <bool LH>
+constexpr bool off32() {
+#ifdef PU_JIT_GEO
+    return PU_OFF32 && !LH && kJitGeo.replica_bytes < (1ull << 32);
+#else
+    return false;   // the unit hooks read their geometry at run time
+#endif
+}
 template <bool LH, int NL, class T>
 __device__ __forceinline__ T off_v(T c) {
 #ifdef PU_JIT_GEO
-    if constexpr (!LH && NL == 1) {   // (measured on the one-level engine; deeper hierarchies keep them folded)
+    if constexpr (off32<LH>() && NL == 1) {
+        // (a geometry value that is no constant at this use stays what it is)
+        if (!__builtin_constant_p(c)) return c;
+        uint32_t lo;
+        asm("s_mov_b32 %0, %1" : "=s"(lo) : "i"((uint32_t)(uint64_t)c));
+        return (T)lo;
+    } else if constexpr (!LH && NL == 1) {   // (measured on the one-level engine; deeper hierarchies keep them folded)
         // two 32-bit moves: a 64-bit SALU move takes only a 32-bit literal
         uint32_t lo, hi;
         asm("s_mov_b32 %0, %1" : "=s"(lo) : "s"((uint32_t)(uint64_t)c));
@@ -77,6 +104,32 @@ __device__ __forceinline__ T off_v(T c) {
     return c;
 }
 #define OFF(x) off_v<LH, NL>(x)
+// An array of a replica's arena (Engine::at).  O32: the replica base and the
+// array's 32-bit byte offset, an element's offset formed in 32 bits; else a
+// plain pointer.  Indices are element counts either way.
+template <class T, bool O32>
+struct Arr;
+template <class T>
+struct Arr<T, false> {
+    T* p;
+    __device__ __forceinline__ Arr(char* base, uint64_t off) : p(reinterpret_cast<T*>(base + off)) {}
+    __device__ __forceinline__ T* ptr() const { return p; }
+    __device__ __forceinline__ T* at(uint64_t i) const { return p + i; }
+    __device__ __forceinline__ T& operator[](uint64_t i) const { return p[i]; }
+    __device__ __forceinline__ T* operator->() const { return p; }
+};
+template <class T>
+struct Arr<T, true> {
+    char* base;
+    uint32_t off;
+    __device__ __forceinline__ Arr(char* b, uint64_t o) : base(b), off((uint32_t)o) {}
+    __device__ __forceinline__ T* ptr() const { return reinterpret_cast<T*>(base + off); }
+    __device__ __forceinline__ T* at(uint64_t i) const {
+        return reinterpret_cast<T*>(base + (uint32_t)(off + (uint32_t)i * (uint32_t)sizeof(T)));
+    }
+    __device__ __forceinline__ T& operator[](uint64_t i) const { return *at(i); }
+    __device__ __forceinline__ T* operator->() const { return ptr(); }
+};
 constexpr uint32_t ST_I = 0, ST_S = 1, ST_E = 2, ST_M = 3, ST_V = 4, ST_B = 5;
 
 // Lane within the wavefront (latency-mode workgroups hold two waves).
@@ -255,13 +308,22 @@ constexpr int kAliveWords = 1;
 static __shared__ uint32_t lds_alive[kAliveWords];
 static __shared__ unsigned long long lds_err;
 // The message loop's state (uncore_body), lane 0 its writer.
+// What every request reads of it, one 16-B record read once per request
+// (replica_steps): the wave reads it whole, lane 0 writes its fields.
+struct alignas(8) LoopHot {
+    uint64_t deadline;     // s_memrealtime at which a time-sliced launch stops
+    int32_t D;             // prime.cpp's running `delay` of the open message
+    uint8_t halted;
+    uint8_t stop;          // replica must stop (engine limit): set by the engine during a request
+    uint8_t general;       // any of PU_KF_MSGHALT, PU_KF_CLOSED, PU_KF_NOHALT: the loop's general path
+    uint8_t req16;         // PU_KF_REQ16
+};
 struct LoopCtl {
+    LoopHot hot;
     int64_t msg_shift;     // PU_KF_CLOSED: core shift at the open message's start
     uint64_t dead_tags;    // PU_KF_MSGHALT: receive threads that have exited
-    uint64_t deadline;     // s_memrealtime at which a time-sliced launch stops
     uint64_t done;         // requests processed in this launch
-    int32_t D;             // prime.cpp's running `delay` of the open message
-    int32_t halted, halted0, skip;
+    int32_t halted0, skip;
     uint32_t flags;
     int32_t last_d;        // latency kernels: the last request's delay (0: none ran), for the resident fast answer
     uint64_t cur;          // index of the request being simulated
@@ -273,7 +335,6 @@ static __shared__ LoopCtl lds_ctl;
 // writes the same wave-uniform value).
 struct EngShared {
     int32_t pool_top;    // sharer-bitmap pool stack (RunState.pool_top)
-    int32_t stop;        // replica must stop (engine limit)
     uint64_t page_next;  // RunState.page_next
     uint64_t last_addr;  // RunState.last_addr
 };
@@ -373,6 +434,10 @@ namespace {
 struct NetCtx {
     AS1 char* qhdr;            // the replica's queue headers (packed: 32 B each; wide: {a, b} of every queue, then c)
     AS1 char* qring;           // ... and rings
+    // PU_OFF32 (o32, a constant wherever a NetCtx is built): qhdr is the replica
+    // base and these are the headers' and rings' 32-bit byte offsets from it
+    bool o32;
+    uint32_t hoff, roff;
     uint32_t router, link_delay, inject;
     uint32_t hdr_c;            // wide headers: byte offset of the c pieces (nqueues x 32)
     uint32_t p0, p1;           // packed headers: the two packet lengths (n counts all visits, n1 those of p1)
@@ -381,8 +446,18 @@ struct NetCtx {
     int w2, blk_len, plen_blk;
 };
 
-__device__ __forceinline__ AS1 v2u64* q_ring(const NetCtx& c, int q) {
-    return reinterpret_cast<AS1 v2u64*>(c.qring) + (size_t)q * PU_QRING;
+// slot i of queue q's ring (o32: its byte offset from the replica base)
+__device__ __forceinline__ uint32_t q_ring_off(const NetCtx& c, int q, uint32_t i) {
+    return c.roff + (uint32_t)q * (uint32_t)(PU_QRING * sizeof(v2u64)) + i * (uint32_t)sizeof(v2u64);
+}
+__device__ __forceinline__ AS1 v2u64* q_ring(const NetCtx& c, int q, uint32_t i) {
+    if (c.o32) return reinterpret_cast<AS1 v2u64*>(c.qhdr + q_ring_off(c, q, i));
+    return reinterpret_cast<AS1 v2u64*>(c.qring) + (size_t)q * PU_QRING + i;
+}
+// the packed 32-B header of queue q
+__device__ __forceinline__ AS1 v4u32* q_hdr(const NetCtx& c, int q) {
+    if (c.o32) return reinterpret_cast<AS1 v4u32*>(c.qhdr + (uint32_t)(c.hoff + (uint32_t)q * (uint32_t)PU_HDR_BYTES));
+    return reinterpret_cast<AS1 v4u32*>(c.qhdr + (uint64_t)q * PU_HDR_BYTES);
 }
 __device__ __forceinline__ AS1 v4u32* q_hdr_ab(const NetCtx& c, int q) {
     return reinterpret_cast<AS1 v4u32*>(c.qhdr + (uint64_t)q * PU_HDR_AB);
@@ -395,16 +470,15 @@ __device__ __forceinline__ AS1 v4u32* q_hdr_c(const NetCtx& c, int q) {
 // (lane l holds intervals l and l+64); dead intervals are not fetched and
 // read as 0.
 __device__ __forceinline__ void ring_load(const NetCtx& c, int q, uint32_t head, uint32_t cnt, RingView& v) {
-    const AS1 v2u64* R = q_ring(c, q);
     const uint32_t ln = (uint32_t)lane_id();
     v = RingView{0, 0, 0, 0};
     if (ln < cnt) {
-        v2u64 a = R[(head + ln) & (PU_QRING - 1)];
+        v2u64 a = *q_ring(c, q, (head + ln) & (PU_QRING - 1));
         v.lf = a.x;
         v.ls = a.y;
     }
     if (ln + 64 < cnt) {
-        v2u64 b = R[(head + 64 + ln) & (PU_QRING - 1)];
+        v2u64 b = *q_ring(c, q, (head + 64 + ln) & (PU_QRING - 1));
         v.hf = b.x;
         v.hs = b.y;
     }
@@ -695,9 +769,8 @@ __device__ __forceinline__ uint64_t tree_op(const NetCtx& c, int q, const RingVi
     wh = wh || jh == fi || jh == si;
     PROF_ADD(PF_T_EDIT, p_e);
     PROF_T(p_w);
-    AS1 v2u64* R = q_ring(c, q);
-    if (wl) R[(head0 + jl) & (PU_QRING - 1)] = v2u64{lf, ls};
-    if (wh) R[(head0 + jh) & (PU_QRING - 1)] = v2u64{hf, hs};
+    if (wl) *q_ring(c, q, (head0 + jl) & (PU_QRING - 1)) = v2u64{lf, ls};
+    if (wh) *q_ring(c, q, (head0 + jh) & (PU_QRING - 1)) = v2u64{hf, hs};
     // the header's copies of the first two interval starts: the new cursor is
     // the old logical index (head - head0) & 127 (0, 1 or 127)
     // (0, 1 or 127: a uniform branch, no selects between the halves)
@@ -818,7 +891,9 @@ __device__ __forceinline__ void q_store_hdr(const NetCtx& c, int q, const QState
             H[1] = b;
             H[0] = a;
         } else {
-            AS1 v4u32* H = reinterpret_cast<AS1 v4u32*>(c.qhdr + (uint64_t)q * PU_HDR_BYTES);
+            // (o32: the offset formed again here, opaque, and not the header
+            // load's address kept in a VGPR pair across the window)
+            AS1 v4u32* H = q_hdr(c, c.o32 ? lane_here(q) : q);
             H[0] = a;
             H[1] = b;
         }
@@ -909,7 +984,7 @@ __device__ __forceinline__ void hdr_load(const NetCtx& c, int q, v4u32& a, v4u32
         b = H[1];
         cc = v4u32{0u, 0u, 0u, 0u};
     } else {
-        const AS1 v4u32* H = reinterpret_cast<const AS1 v4u32*>(c.qhdr + (uint64_t)q * PU_HDR_BYTES);
+        const AS1 v4u32* H = q_hdr(c, q);
         a = H[0];
         b = H[1];
         cc = v4u32{0u, 0u, 0u, 0u};
@@ -978,16 +1053,33 @@ __device__ __forceinline__ int net_route_link(const NetCtx& c, int h, int sx, in
 template <bool LH>
 __device__ __forceinline__ void ring_dma(const NetCtx& c, int q, uint32_t head, uint32_t cnt, int slot) {
     const int ln = lane_id();
-    const AS1 v2u64* R = q_ring(c, q);
     // logical order (RingView): LDS position l <- interval l from the cursor
     // (dead positions re-read the last live slot: min instead of a compare and select)
     const uint32_t last = cnt - 1;
-    const AS1 v2u64* ga = R + ((head + __builtin_elementwise_min((uint32_t)ln, last)) & (PU_QRING - 1));
-    const AS1 v2u64* gb = R + ((head + __builtin_elementwise_min((uint32_t)ln + 64, last)) & (PU_QRING - 1));
+    const uint32_t ia = (head + __builtin_elementwise_min((uint32_t)ln, last)) & (PU_QRING - 1);
+    const uint32_t ib = (head + __builtin_elementwise_min((uint32_t)ln + 64, last)) & (PU_QRING - 1);
     const uint32_t la = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) v2u64*)ring_slot<LH>(slot);
     const uint32_t lo = __builtin_amdgcn_readfirstlane(la), hi = lo + 64 * sizeof(v2u64);
     unsigned keep;
     // lgkmcnt(0): the slot's previous ds_reads have returned before it is refilled
+    if (c.o32) {   // the replica base as the scalar address, the slot's offset per lane
+        asm volatile(
+            "s_waitcnt lgkmcnt(0)\n\t"
+            "s_mov_b32 %0, m0\n\t"
+            "s_mov_b32 m0, %3\n\t"
+            "s_nop 0\n\t"
+            "global_load_lds_dwordx4 %1, %5\n\t"
+            "s_mov_b32 m0, %4\n\t"
+            "s_nop 0\n\t"
+            "global_load_lds_dwordx4 %2, %5\n\t"
+            "s_mov_b32 m0, %0"
+            : "=&s"(keep)
+            : "v"(q_ring_off(c, q, ia)), "v"(q_ring_off(c, q, ib)), "s"(lo), "s"(hi), "s"((uint64_t)c.qhdr)
+            : "memory");
+        return;
+    }
+    const AS1 v2u64* ga = q_ring(c, q, ia);
+    const AS1 v2u64* gb = q_ring(c, q, ib);
     asm volatile(
         "s_waitcnt lgkmcnt(0)\n\t"
         "s_mov_b32 %0, m0\n\t"
@@ -1024,6 +1116,21 @@ __device__ __forceinline__ void lds_dma(const AS1 char* src, uint32_t lds_base) 
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
                      "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
                      : "=&s"(keep) : "v"(src), "s"(lo) : "memory");
+}
+// The same from the wave-uniform `base` + the lane's 32-bit offset `voff` (no
+// immediate offset: the instruction would add it to the LDS address as well).
+template <bool X4>
+__device__ __forceinline__ void lds_dma_o32(const char* base, uint32_t voff, uint32_t lds_base) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(lds_base);
+    unsigned keep;
+    if (X4)
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(voff), "s"(lo), "s"(base) : "memory");
+    else
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                     "global_load_lds_dword %1, %3\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(voff), "s"(lo), "s"(base) : "memory");
 }
 template <class T>
 __device__ __forceinline__ uint32_t lds_addr(T* p) {
@@ -1064,6 +1171,20 @@ static __shared__ uint32_t lds_dir_w[2][32];
 #endif
 template <bool LH, bool WIDE>
 constexpr bool pair_window() { return PU_PAIR_WINDOW && !LH && !WIDE; }
+// The replica's queue headers and rings into a NetCtx (NetCtx.o32).
+template <bool LH, int NL, bool WIDE>
+__device__ __forceinline__ void net_arrays(NetCtx& c, const Geo* __restrict__ g, AS1 char* base) {
+    c.o32 = off32<LH>() && !WIDE;
+    if (c.o32) {
+        c.qhdr = c.qring = base;
+        c.hoff = (uint32_t)OFF(g->off_qhdr);
+        c.roff = (uint32_t)OFF(g->off_qring);
+    } else {
+        c.qhdr = base + OFF(g->off_qhdr);
+        c.qring = base + OFF(g->off_qring);
+        c.hoff = c.roff = 0;
+    }
+}
 template <bool LH, int NL, bool WIDE>
 __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char* base_in, int src, int dst, int len,
                                                  uint64_t timer, uint32_t& hq_head, bool& pair, int len2,
@@ -1072,8 +1193,7 @@ __device__ __forceinline__ uint64_t net_transmit(const Geo* __restrict__ g, char
     PROF_T(p_pre);
     NetCtx c;
     AS1 char* base = (AS1 char*)(char*)uni64((uint64_t)base_in);
-    c.qhdr = base + OFF(g->off_qhdr);
-    c.qring = base + OFF(g->off_qring);
+    net_arrays<LH, NL, WIDE>(c, g, base);
     c.hdr_c = (uint32_t)g->nqueues * PU_HDR_AB;
     c.p0 = (uint32_t)g->header_flits;     // packed headers: 0-byte messages ...
     c.p1 = (uint32_t)g->plen_blk;         // ... and blocks
@@ -1538,22 +1658,23 @@ struct Engine {
 
     __device__ __forceinline__ void init_shared(int32_t pool_top, uint64_t page_next, uint64_t last_addr) const {
         lds_eng.pool_top = pool_top;
-        lds_eng.stop = 0;
         lds_eng.page_next = page_next;
         lds_eng.last_addr = last_addr;
     }
 
 
+    static constexpr bool O32 = off32<LH>() && !WIDE;
     template <class T>
-    __device__ __forceinline__ T* at(uint64_t off) const {
-        return reinterpret_cast<T*>(base + off);
+    using A = Arr<T, O32>;
+    template <class T>
+    __device__ __forceinline__ A<T> at(uint64_t off) const {
+        return A<T>(base, off);
     }
 
     // ------------------------------------------------------------ network
     __device__ __forceinline__ NetCtx net_ctx() const {
         NetCtx c;
-        c.qhdr = (AS1 char*)base + OFF(g->off_qhdr);
-        c.qring = (AS1 char*)base + OFF(g->off_qring);
+        net_arrays<LH, NL, WIDE>(c, g, (AS1 char*)base);
         c.hdr_c = (uint32_t)g->nqueues * PU_HDR_AB;
         c.p0 = c.p1 = (uint32_t)g->bus_latency;   // packed headers: a bus queue sees one packet length
         c.router = (uint32_t)g->router_delay;
@@ -1584,7 +1705,7 @@ struct Engine {
     }
 
     // ------------------------------------------------------------ sets
-    __device__ __forceinline__ void set_load(SetView& v, const LineMeta* meta, const int64_t* ts,
+    __device__ __forceinline__ void set_load(SetView& v, A<LineMeta> meta, A<int64_t> ts,
                                              uint64_t nsets, uint64_t nways, int offbits, int idxbits,
                                              uint64_t cache_index, uint64_t addr) const {
         v.set = set_index(addr, offbits, nsets);
@@ -1594,7 +1715,7 @@ struct Engine {
         set_chunk(v, meta, ts, nways, 0);
     }
     // lane w <- way w0 + w of the set
-    __device__ __forceinline__ void set_chunk(SetView& v, const LineMeta* meta, const int64_t* ts, uint64_t nways,
+    __device__ __forceinline__ void set_chunk(SetView& v, A<LineMeta> meta, A<int64_t> ts, uint64_t nways,
                                               uint32_t w0) const {
         v.w0 = w0;
         const uint64_t w = (uint64_t)w0 + (uint64_t)ln;
@@ -1617,7 +1738,7 @@ struct Engine {
     // the lane holding `way` (a way of the chunk held)
     static __device__ __forceinline__ int wl(const SetView& v, int way) { return way - (int)v.w0; }
     // Cache::accessLine (cache.cpp:184-202): the first matching way
-    __device__ __forceinline__ int set_find(SetView& v, const LineMeta* meta, const int64_t* ts, uint64_t nways,
+    __device__ __forceinline__ int set_find(SetView& v, A<LineMeta> meta, A<int64_t> ts, uint64_t nways,
                                             int prog) const {
         if (!wide(nways)) {
             uint64_t m = ballot((uint64_t)ln < nways && v.mst != ST_I && v.mid == prog && v.mtag == v.tag);
@@ -1633,7 +1754,7 @@ struct Engine {
     }
     // Cache::replaceLine (cache.cpp:204-235): first invalid way, else LRU
     // (strictly smaller timestamp, lowest way on ties).  Sets tag/id only.
-    __device__ __forceinline__ int set_replace(SetView& v, LineMeta* meta, const int64_t* ts, uint64_t nways,
+    __device__ __forceinline__ int set_replace(SetView& v, A<LineMeta> meta, A<int64_t> ts, uint64_t nways,
                                                int offbits, int idxbits, int prog, uint32_t* old_state,
                                                uint64_t* old_addr, int* old_prog) const {
         int way = -1;
@@ -1685,13 +1806,13 @@ struct Engine {
         }
         return way;
     }
-    __device__ __forceinline__ void set_state(SetView& v, LineMeta* meta, int way, uint32_t st) const {
+    __device__ __forceinline__ void set_state(SetView& v, A<LineMeta> meta, int way, uint32_t st) const {
         if (ln == wl(v, way)) {
             v.mst = st;
             meta[v.line0 + (uint64_t)way].state = st;
         }
     }
-    __device__ __forceinline__ void set_ts(SetView& v, int64_t* ts, int way, int64_t t) const {
+    __device__ __forceinline__ void set_ts(SetView& v, A<int64_t> ts, int way, int64_t t) const {
         if (ln == wl(v, way)) {
             v.mts = t;
             ts[v.line0 + (uint64_t)way] = t;
@@ -1722,7 +1843,7 @@ struct Engine {
     template <int K>
     __device__ __forceinline__ void count(uint64_t off_cnt, int cid, int which) const {
         if constexpr (kCntSum) stat_add(SN_CNT0 + 4 * K + which, 1);
-        else gatomic_add_u64_lane0(at<uint64_t>(off_cnt) + (size_t)cid * 4 + which, 1ull);
+        else gatomic_add_u64_lane0(at<uint64_t>(off_cnt).at((size_t)cid * 4 + which), 1ull);
     }
 
     // Dram::access (dram.cpp:43-47) at cycle t for line address addr: the
@@ -1737,7 +1858,7 @@ struct Engine {
         const uint64_t bank = row & (uint64_t)(g->dram_banks - 1);
         const uint64_t page = (row >> g->dram_bank_shift) + 1;   // + 1: 0 means closed
         t = (int64_t)uni64((uint64_t)t);
-        DramBank* B = at<DramBank>(OFF(g->off_dram)) + bank;
+        DramBank* B = at<DramBank>(OFF(g->off_dram)).at(bank);
         const int64_t ready = (int64_t)uni64((uint64_t)B->ready);
         const uint64_t open = uni64(B->open);
         const int64_t start = ready > t ? ready : t;
@@ -1830,12 +1951,13 @@ struct Engine {
                  : (s & 0xFFFull) | ((s & 0xFFF000ull) << 4) | ((s & 0xFFF000000ull) << 8) |
                        ((s & 0xFFF000000000ull) << 12);
     }
-    __device__ __forceinline__ uint64_t* pool_of(uint64_t idx) const {
-        return at<uint64_t>(OFF(g->dir.off_pool)) + idx * (uint64_t)g->dir.nwords;
+    // word w of pool entry idx
+    __device__ __forceinline__ uint64_t* pool_of(uint64_t idx, int w) const {
+        return at<uint64_t>(OFF(g->dir.off_pool)).at(idx * (uint64_t)g->dir.nwords + (uint64_t)w);
     }
     // bitmap words base .. base+63 of pool entry idx, lane k holding word base + k
     __device__ __forceinline__ uint64_t pool_word(uint64_t idx, int base = 0) const {
-        return base + ln < g->dir.nwords ? pool_of(idx)[base + ln] : 0ull;
+        return base + ln < g->dir.nwords ? *pool_of(idx, base + ln) : 0ull;
     }
     __device__ __forceinline__ void pool_release(uint32_t nsh, uint64_t sh) {
         if (nsh != PU_SH_POOL) return;
@@ -1847,7 +1969,7 @@ struct Engine {
         const int32_t pt = (int32_t)uni32((uint32_t)lds_eng.pool_top);
         if (pt <= 0) {
             err_or(PU_ERRF_POOL);
-            lds_eng.stop = 1;
+            lds_ctl.hot.stop = 1;
             return false;
         }
         lds_eng.pool_top = pt - 1;
@@ -1882,7 +2004,7 @@ struct Engine {
     __device__ __forceinline__ void add_sharer(uint32_t& nsh, uint64_t& sh, int cid) {
         if (nsh == PU_SH_POOL) {
             if (ln == ((cid >> 6) & 63)) {
-                uint64_t* P = pool_of(sh) + (cid >> 6);
+                uint64_t* P = pool_of(sh, cid >> 6);
                 *P = *P | (1ull << (cid & 63));
             }
             return;
@@ -1916,7 +2038,7 @@ struct Engine {
                 if ((id >> 6) == base + ln) w |= 1ull << (id & 63);
             }
             if ((c >> 6) == base + ln) w |= 1ull << (c & 63);
-            if (base + ln < g->dir.nwords) pool_of(idx)[base + ln] = w;
+            if (base + ln < g->dir.nwords) *pool_of(idx, base + ln) = w;
         }
         nsh = PU_SH_POOL;
         sh = idx;
@@ -2023,8 +2145,15 @@ struct Engine {
         if (D.nways > 32) return 0;
         const uint64_t set = set_index(addr, D.offbits, D.nsets);
         const uint64_t line0 = (uint64_t)(((uint32_t)home * (uint32_t)D.csets + (uint32_t)(set >> D.cset_shift)) * (uint32_t)D.nways);
-        if ((uint64_t)ln < D.nways) {
-            const AS1 char* lp = (const AS1 char*)(const char*)(at<DirLine>(OFF(D.off_line)) + line0 + (uint64_t)ln);
+        if constexpr (O32) {
+            if ((uint64_t)ln < D.nways) {
+                const uint32_t lo = (uint32_t)OFF(D.off_line) + ((uint32_t)line0 + (uint32_t)ln) * (uint32_t)sizeof(DirLine);
+                lds_dma_o32<true>(base, lo, lds_addr(&lds_dir_a[0]));
+                lds_dma_o32<false>(base, lo + 16, lds_addr(&lds_dir_w[0][0]));
+                lds_dma_o32<false>(base, lo + 20, lds_addr(&lds_dir_w[1][0]));
+            }
+        } else if ((uint64_t)ln < D.nways) {
+            const AS1 char* lp = (const AS1 char*)(const char*)at<DirLine>(OFF(D.off_line)).at(line0 + (uint64_t)ln);
             lds_dma<true>(lp, lds_addr(&lds_dir_a[0]));
             lds_dma<false>(lp + 16, lds_addr(&lds_dir_w[0][0]));
             lds_dma<false>(lp + 20, lds_addr(&lds_dir_w[1][0]));
@@ -2044,7 +2173,7 @@ struct Engine {
         const bool shared = g->shared_llc != 0;
         constexpr int last = NL - 1;
         const int blk = (int)g->lv[last].block;
-        DirLine* lines = at<DirLine>(OFF(D.off_line));
+        const A<DirLine> lines = at<DirLine>(OFF(D.off_line));
         // home_stat[home] = 1 (read by the verbose report only)
         if (!kCntSum && ln == (home & 63)) at<uint32_t>(OFF(D.off_alive))[home] = 1u;
         const uint64_t set = set_index(r.addr, D.offbits, D.nsets);
@@ -2080,7 +2209,7 @@ struct Engine {
         // program ids: the 10-bit field decides unless either side is escaped;
         // the side array is read only then (ids >= 1023 or negative)
         const uint32_t want10 = prog10(r.prog), m_p10 = (uint32_t)(m.w >> 54);
-        int32_t* side = at<int32_t>(OFF(D.off_prog));
+        const A<int32_t> side = at<int32_t>(OFF(D.off_prog));
         int32_t m_prog = (int32_t)m_p10;
         if (want10 == PU_DIR_PROG_ESC || ballot(mine && m_p10 == PU_DIR_PROG_ESC)) {
             if (mine && m_p10 == PU_DIR_PROG_ESC) m_prog = side[line0 + (uint64_t)ln];
@@ -2272,8 +2401,8 @@ struct Engine {
     __device__ __forceinline__ uint32_t mesi(int cid, const Req& r, int64_t timer) {
         const LevelGeo& L = g->lv[LV];
         constexpr bool kLast = LV == NL - 1;
-        LineMeta* meta = at<LineMeta>(OFF(L.off_meta));
-        int64_t* tsa = at<int64_t>(OFF(L.off_ts));
+        const A<LineMeta> meta = at<LineMeta>(OFF(L.off_meta));
+        const A<int64_t> tsa = at<int64_t>(OFF(L.off_ts));
         SetView v;
         PROF_T(p_set);
         set_load(v, meta, tsa, L.nsets, L.nways, L.offbits, L.idxbits, (uint64_t)cid, r.addr);
@@ -2407,7 +2536,7 @@ struct Engine {
     __device__ __forceinline__ bool snoop(int cid, const Req& r, int mode) {
         constexpr int last = NL - 1;
         const LevelGeo& L = g->lv[last];
-        LineMeta* meta = at<LineMeta>(OFF(L.off_meta));
+        const A<LineMeta> meta = at<LineMeta>(OFF(L.off_meta));
         const uint64_t set = set_index(r.addr, L.offbits, L.nsets);
         const uint64_t tag = r.addr >> (L.offbits + L.idxbits);
         bool any = false;
@@ -2416,9 +2545,9 @@ struct Engine {
             int myway = -1;
             uint32_t myst = ST_I;
             if (c < L.ncaches && c != cid) {
-                const LineMeta* sp = meta + ((uint64_t)c * L.nsets + set) * L.nways;
+                const uint64_t s0 = ((uint64_t)c * L.nsets + set) * L.nways;
                 for (uint64_t w = L.nways; w-- > 0;) {      // lowest matching way wins
-                    const LineMeta m = sp[w];
+                    const LineMeta m = meta[s0 + w];
                     if (m.state != ST_I && m.id == r.prog && m.tag == tag) {
                         myway = (int)w;
                         myst = m.state;
@@ -2446,8 +2575,8 @@ struct Engine {
     __device__ __forceinline__ uint32_t mesi_bus(int cid, const Req& r, int64_t timer) {
         const LevelGeo& L = g->lv[LV];
         constexpr bool kLast = LV == NL - 1;
-        LineMeta* meta = at<LineMeta>(OFF(L.off_meta));
-        int64_t* tsa = at<int64_t>(OFF(L.off_ts));
+        const A<LineMeta> meta = at<LineMeta>(OFF(L.off_meta));
+        const A<int64_t> tsa = at<int64_t>(OFF(L.off_ts));
         SetView v;
         set_load(v, meta, tsa, L.nsets, L.nways, L.offbits, L.idxbits, (uint64_t)cid, r.addr);
         mark_alive(LV, cid);
@@ -2530,7 +2659,7 @@ struct Engine {
     // first empty slot.
     __device__ __forceinline__ uint64_t page_translate(int prog, uint64_t vpage) {
         const TlbGeo& T = g->tlb;
-        PageEnt* tab = at<PageEnt>(OFF(T.off_pages));
+        const A<PageEnt> tab = at<PageEnt>(OFF(T.off_pages));
         const uint64_t mask = T.pages_cap - 1;
         uint64_t x = vpage * 0x9E3779B97F4A7C15ull ^ ((uint64_t)(uint32_t)prog * 0xC2B2AE3D27D4EB4Full);
         x ^= x >> 31;
@@ -2549,7 +2678,7 @@ struct Engine {
                 const uint64_t pp = uni64(lds_eng.page_next);
                 if (pp * 4 >= T.pages_cap * 3) {              // keep probes short; engine limit
                     err_or(PU_ERRF_PAGES);
-                    lds_eng.stop = 1;
+                    lds_ctl.hot.stop = 1;
                 }
                 lds_eng.page_next = pp + 1;
                 if (ln == fe) tab[slot] = PageEnt{vpage, prog, 1u, pp, 0ull};
@@ -2558,7 +2687,7 @@ struct Engine {
             h = (h + 64) & mask;
         }
         err_or(PU_ERRF_PAGES);
-        lds_eng.stop = 1;
+        lds_ctl.hot.stop = 1;
         return 0;
     }
 
@@ -2566,9 +2695,9 @@ struct Engine {
     // request's address becomes physical (ppage << log2(page) | offset).
     __device__ __forceinline__ int tlb_translate(int core, Req& r, int64_t timer) {
         const TlbGeo& T = g->tlb;
-        LineMeta* meta = at<LineMeta>(OFF(T.off_meta));
-        int64_t* tsa = at<int64_t>(OFF(T.off_ts));
-        uint64_t* ppa = at<uint64_t>(OFF(T.off_ppage));
+        const A<LineMeta> meta = at<LineMeta>(OFF(T.off_meta));
+        const A<int64_t> tsa = at<int64_t>(OFF(T.off_ts));
+        const A<uint64_t> ppa = at<uint64_t>(OFF(T.off_ppage));
         SetView v;
         set_load(v, meta, tsa, T.nsets, T.nways, T.offbits, T.idxbits, (uint64_t)core, r.addr);
         const uint64_t mypp = !wide(T.nways) && (uint64_t)ln < T.nways ? ppa[v.line0 + (uint64_t)ln] : 0ull;
@@ -2617,7 +2746,7 @@ struct Engine {
     }
 
     __device__ __forceinline__ void flush_stats() {
-        EngineStats* S = at<EngineStats>(OFF(g->off_stats));
+        EngineStats* S = at<EngineStats>(OFF(g->off_stats)).ptr();
         if constexpr (kCntSum) {   // lane k: per-level sum k
             const uint64_t v = ln < SN_COUNT - SN_CNT0 ? lds_stat[SN_CNT0 + ln] : 0ull;
             if (v) atomic_add_u64(&S->lvl_cnt[0][0] + ln, v);
@@ -2722,6 +2851,17 @@ template <int NL, bool SLICED, bool LH>
 __device__ __forceinline__ bool replica_steps(Engine<NL, LH>& e, const pu_req* __restrict__ reqs,
                                               int32_t* __restrict__ delays, uint64_t b, uint64_t end,
                                               uint64_t* __restrict__ pos_out);
+// What a launch (or a resident command) sets of the loop's state from its
+// flags and the replica's halted flag h0, by lane 0: the flags, the loop's
+// path, and `halted` (not inherited under PU_KF_NOHALT); no engine stop yet.
+constexpr uint32_t PU_KF_GENERAL = PU_KF_MSGHALT | PU_KF_CLOSED | PU_KF_NOHALT;
+__device__ __forceinline__ void loop_launch_state(uint32_t flags, int32_t h0) {
+    lds_ctl.flags = flags;
+    // the record's four bytes {halted, stop, general, req16} as one word
+    const uint32_t w = ((flags & PU_KF_NOHALT) || !h0 ? 0u : 1u) | ((flags & PU_KF_GENERAL) ? 1u << 16 : 0u) |
+                       ((flags & PU_KF_REQ16) ? 1u << 24 : 0u);
+    __builtin_memcpy(&lds_ctl.hot.halted, &w, sizeof(w));
+}
 // The message loop's state from the replica's RunState (lane 0 into lds_ctl,
 // lds_eng), counters zeroed: the start of a launch's work on one replica.
 template <int NL, bool LH>
@@ -2733,17 +2873,16 @@ __device__ __forceinline__ void replica_begin(Engine<NL, LH>& e, uint64_t deadli
     // The message loop's own state lives in LDS (lane 0 writes, every lane reads
     // it back wave-uniform): nothing of it stays in registers across the
     // inlined access(), whose register budget is tight (5 waves/SIMD).
-    RunState* rs = e.template at<RunState>(OFF(e.g->off_run));
+    RunState* rs = e.template at<RunState>(OFF(e.g->off_run)).ptr();
     if (e.ln == 0) {
         const int32_t h0 = rs->halted;
-        lds_ctl.D = rs->batch_delay;
+        lds_ctl.hot.D = rs->batch_delay;
         lds_ctl.halted0 = h0;
-        lds_ctl.halted = (flags & PU_KF_NOHALT) ? 0 : h0;
+        loop_launch_state(flags, h0);
         lds_ctl.skip = rs->skip_msg;
-        lds_ctl.flags = flags;
         lds_ctl.msg_shift = rs->msg_shift;
         lds_ctl.dead_tags = rs->dead_tags;
-        lds_ctl.deadline = deadline;
+        lds_ctl.hot.deadline = deadline;
         lds_ctl.done = 0;
         lds_ctl.cur = 0;
         lds_ctl.limit_at = UINT64_MAX;
@@ -2768,65 +2907,98 @@ __device__ __forceinline__ bool replica_steps(Engine<NL, LH>& e, const pu_req* _
                                               int32_t* __restrict__ delays, uint64_t b, uint64_t end,
                                               uint64_t* __restrict__ pos_out) {
     uint64_t i = b;
+    if (e.ln == 0) {
+        lds_ctl.cur = b;
+        if (!lds_ctl.hot.general) lds_ctl.done -= b;   // the plain path runs every request: counted after the loop
+    }
+    __builtin_amdgcn_wave_barrier();
+    // what the part after the request needs of the part before it, in one
+    // scalar register: the launch's path and flags, and whether the core is one
+    constexpr uint32_t CX_CORE_OK = 1u, CX_GENERAL = 2u, CX_CLOSED = 4u, CX_MSGHALT = 8u, CX_NOHALT = 16u;
     for (; i < end; i++) {
+        // the loop's state: one 16-B LDS read per request
+        v4u32 hw;
+        __builtin_memcpy(&hw, &lds_ctl.hot, sizeof(hw));
+        hw = uni4(hw);
+        // hw.w: halted | stop << 8 | general << 16 | req16 << 24 (LoopHot)
         // the slice's clock, every fourth request (a slice still ends between
         // requests, at most three requests later)
-        if (SLICED && (i & 3) == 0 && __builtin_amdgcn_s_memrealtime() >= uni64(lds_ctl.deadline)) break;
-        if (uni32((uint32_t)lds_ctl.halted)) break;   // the rest is zero-filled below
+        if (SLICED && (i & 3) == 0 && __builtin_amdgcn_s_memrealtime() >= u64of(hw.x, hw.y)) break;
+        if (hw.w & 0xFFFFu) break;   // halted, or stopped by an engine limit: the rest is zero-filled below
         PROF_T(p_loop);
-        const uint32_t fl = uni32(lds_ctl.flags);
-        const pu_req q = (fl & PU_KF_REQ16) ? req_unpack16(reinterpret_cast<const v2u64*>(reqs)[i]) : reqs[i];
+        const pu_req q = (hw.w >> 24) ? req_unpack16(reinterpret_cast<const v2u64*>(reqs)[i]) : reqs[i];
         const bool core_ok = q.core >= 0 && q.core < e.g->num_cores;
-        if (e.ln == 0) lds_ctl.cur = i;
-        if (q.batch_start && e.ln == 0) {
-            lds_ctl.D = 0;
-            lds_ctl.skip = (fl & PU_KF_MSGHALT) ? (int32_t)((lds_ctl.dead_tags >> (q.tag & 63)) & 1) : 0;
-            if ((fl & PU_KF_CLOSED) && core_ok)
-                lds_ctl.msg_shift = e.template at<int64_t>(OFF(e.g->off_core_shift))[q.core];
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (uni32((uint32_t)lds_ctl.skip)) {     // PU_KF_MSGHALT: this message's receive thread has exited
-            if (e.ln == 0) {
-                delays[i] = 0;
-                if constexpr (LH) lds_ctl.last_d = 0;
+        uint32_t cx = core_ok ? CX_CORE_OK : 0u;
+        // prime.cpp:122: a message starts with delay 0 (held here until the one store after the request)
+        const int32_t D0 = q.batch_start ? 0 : (int32_t)hw.z;
+        int64_t shift = 0;
+        if (hw.w & 0xFF0000u) {   // PU_KF_MSGHALT, PU_KF_CLOSED or PU_KF_NOHALT: skipped messages, closed-loop core shifts
+            const uint32_t fl = uni32(lds_ctl.flags);
+            cx |= CX_GENERAL | ((fl & PU_KF_CLOSED) ? CX_CLOSED : 0u) | ((fl & PU_KF_MSGHALT) ? CX_MSGHALT : 0u) |
+                  ((fl & PU_KF_NOHALT) ? CX_NOHALT : 0u);
+            if (q.batch_start && e.ln == 0) {
+                lds_ctl.skip = (fl & PU_KF_MSGHALT) ? (int32_t)((lds_ctl.dead_tags >> (q.tag & 63)) & 1) : 0;
+                if ((fl & PU_KF_CLOSED) && core_ok)
+                    lds_ctl.msg_shift = e.template at<int64_t>(OFF(e.g->off_core_shift))[q.core];
             }
-            continue;
+            __builtin_amdgcn_wave_barrier();
+            if (uni32((uint32_t)lds_ctl.skip)) {     // PU_KF_MSGHALT: this message's receive thread has exited
+                if (e.ln == 0) {
+                    lds_ctl.hot.D = D0;
+                    lds_ctl.cur = i + 1;
+                    delays[i] = 0;
+                    if constexpr (LH) lds_ctl.last_d = 0;
+                }
+                __builtin_amdgcn_wave_barrier();
+                continue;
+            }
+            if (fl & PU_KF_CLOSED) shift = (int64_t)uni64((uint64_t)lds_ctl.msg_shift);
         }
+        cx = uni32(cx);
+        asm volatile("" : "+s"(cx));
         PROF_ADD(PF_REQ, p_loop);
-        const int64_t shift = (fl & PU_KF_CLOSED) ? (int64_t)uni64((uint64_t)lds_ctl.msg_shift) : 0;
-        const int64_t t = q.timer + shift + (int32_t)uni32((uint32_t)lds_ctl.D);
+        const int64_t t = q.timer + shift + D0;
         Req r{q.addr, q.prog_id, (int32_t)q.mem_type};
-        int d = e.access(q.core, r, t);
-        if (e.ln == 0) {
-            const int32_t D = lds_ctl.D + d - 1;
-            lds_ctl.D = D;
-            lds_ctl.done++;
+        const int d = (int)uni32((uint32_t)e.access(q.core, r, t));
+        const int32_t D = D0 + d - 1;
+        if (e.ln == 0) {   // everything the request leaves behind, under one lane mask
+            lds_ctl.hot.D = D;
+            if (cx & CX_GENERAL) lds_ctl.done++;
+            lds_ctl.cur = i + 1;
             delays[i] = d;
             if constexpr (LH) lds_ctl.last_d = d;
-            if (core_ok) {
+            if (cx & CX_CORE_OK) {
                 e.template at<int64_t>(OFF(e.g->off_completion))[q.core] = t + d;
-                if (lds_ctl.flags & PU_KF_CLOSED)
+                if (cx & CX_CLOSED)
                     e.template at<int64_t>(OFF(e.g->off_core_shift))[q.core] = lds_ctl.msg_shift + D;
             }
             if (D < 0) {                         // prime.cpp:130-134
                 err_or(PU_ERRF_NEG_DELAY);
-                if (lds_ctl.flags & PU_KF_MSGHALT) {
+                if (cx & CX_MSGHALT) {
                     lds_ctl.skip = 1;
-                    lds_ctl.dead_tags |= 1ull << (q.tag & 63);
-                } else if (!(lds_ctl.flags & PU_KF_NOHALT)) {
-                    lds_ctl.halted = 1;
+                    // (rare: the message's tag read again; 16-B records carry tag 0)
+                    const uint32_t tag = (lds_ctl.flags & PU_KF_REQ16) ? 0u : (uint32_t)reqs[i].tag;
+                    lds_ctl.dead_tags |= 1ull << (tag & 63);
+                } else if (!(cx & CX_NOHALT)) {
+                    lds_ctl.hot.halted = 1;
                 }
-            }
-            if (lds_eng.stop) {                  // engine limit hit: cannot continue exactly
-                lds_ctl.halted = 1;
-                lds_ctl.skip = 0;
             }
         }
         __builtin_amdgcn_wave_barrier();
         PROF_ADD(PF_LOOP, p_loop);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no staging DMA outlives the loop
-    if (i < end && uni32((uint32_t)lds_ctl.halted)) {
+    if (e.ln == 0) {
+        if (!lds_ctl.hot.general) lds_ctl.done += i;
+        // an engine limit hit during the last request run: the replica cannot
+        // continue exactly (the loop left before the next request, if there was one)
+        if (lds_ctl.hot.stop) {
+            lds_ctl.hot.halted = 1;
+            lds_ctl.skip = 0;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (i < end && uni32((uint32_t)lds_ctl.hot.halted)) {
         // the reference's handler thread has exited (prime.cpp:130-134):
         // nothing more is simulated; the rest of the range reads 0, written
         // by the whole wave at once
@@ -2841,10 +3013,10 @@ __device__ __forceinline__ bool replica_steps(Engine<NL, LH>& e, const pu_req* _
 // replica_loop (and, in latency mode, after the header image went back).
 template <int NL, bool LH>
 __device__ __forceinline__ void replica_close(Engine<NL, LH>& e) {
-    RunState* rs = e.template at<RunState>(OFF(e.g->off_run));
+    RunState* rs = e.template at<RunState>(OFF(e.g->off_run)).ptr();
     if (e.ln == 0) {
-        rs->batch_delay = lds_ctl.D;
-        rs->halted = (lds_ctl.flags & PU_KF_NOHALT) ? (lds_ctl.halted0 | lds_ctl.halted) : lds_ctl.halted;
+        rs->batch_delay = lds_ctl.hot.D;
+        rs->halted = (lds_ctl.flags & PU_KF_NOHALT) ? (lds_ctl.halted0 | lds_ctl.hot.halted) : lds_ctl.hot.halted;
         rs->skip_msg = lds_ctl.skip;
         rs->msg_shift = lds_ctl.msg_shift;
         rs->dead_tags = lds_ctl.dead_tags;
@@ -3020,12 +3192,10 @@ __device__ __forceinline__ void resident_body(const Geo* __restrict__ g, char* _
         if (e.ln == 0) {
             const int32_t h0 = lds_res.halted;
             lds_ctl.halted0 = h0;
-            lds_ctl.halted = (fl & PU_KF_NOHALT) ? 0 : h0;
-            lds_ctl.flags = fl;
+            loop_launch_state(fl, h0);
             lds_ctl.cur = 0;
             lds_ctl.limit_at = UINT64_MAX;
             lds_ctl.last_d = 0;
-            lds_eng.stop = 0;
             lds_hq_head = 0;
             lds_main_done = 0;
         }
@@ -3039,7 +3209,7 @@ __device__ __forceinline__ void resident_body(const Geo* __restrict__ g, char* _
         if (e.ln == 0) {
             *(volatile AS3 uint32_t*)&lds_main_done = 1u;
             // replica_close's halted rule
-            lds_res.halted = (fl & PU_KF_NOHALT) ? (lds_ctl.halted0 | lds_ctl.halted) : lds_ctl.halted;
+            lds_res.halted = (fl & PU_KF_NOHALT) ? (lds_ctl.halted0 | lds_ctl.hot.halted) : lds_ctl.hot.halted;
         }
         // The fast answer: a one-request command that raised no error bit, on a
         // configuration without TLB translation, needs nothing but its delay,
@@ -3073,7 +3243,7 @@ __device__ __forceinline__ void resident_body(const Geo* __restrict__ g, char* _
     }
     if (e.ln == 0) {
         lds_ctl.flags = 0u;                           // replica_close writes lds_ctl.halted as the run state's
-        lds_ctl.halted = lds_res.halted;
+        lds_ctl.hot.halted = (uint8_t)(lds_res.halted != 0);
     }
     replica_close<NL, LH>(e);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");

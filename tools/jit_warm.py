@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 # this process and its workers never touch the GPU: the library may start the
 # offline compiler (hipcc) here, and only here (jit.cpp offline_allowed)
 os.environ["PRIMEUNCORE_JIT_OFFLINE"] = "1"
+ENV_EXTRA = os.environ.get("PRIMEUNCORE_JIT_EXTRA")   # the caller's own options, for every configuration without its own
 
 
 def configs():
@@ -51,6 +52,21 @@ def configs():
         out.extend(pair_window_configs())
     except ImportError:
         pass
+    return [(n, c, "") for n, c in out] + extra_option_configs()
+
+
+def extra_option_configs():
+    """Configurations a GPU test also runs with extra compile options
+    (PRIMEUNCORE_JIT_EXTRA, part of the cache key): (name, config, options)."""
+    import primesim_amd as P
+    out = []
+    try:
+        from offsets_loop_cases import JIT_EXTRA_OFF64, OFFSET_GOLDENS
+        for g in OFFSET_GOLDENS:
+            out.append((f"{g}.xml {JIT_EXTRA_OFF64}", P.load_config(os.path.join(ROOT, "tests", "golden", f"{g}.xml")),
+                        JIT_EXTRA_OFF64))
+    except ImportError:
+        pass
     return out
 
 
@@ -70,7 +86,13 @@ def live_source_tags() -> set:
 
 
 def _warm(item):
-    name, cfg_bytes = item
+    name, cfg_bytes, extra = item
+    if extra:       # the library reads it when it compiles (jit.cpp options)
+        os.environ["PRIMEUNCORE_JIT_EXTRA"] = extra
+    elif ENV_EXTRA is None:
+        os.environ.pop("PRIMEUNCORE_JIT_EXTRA", None)
+    else:
+        os.environ["PRIMEUNCORE_JIT_EXTRA"] = ENV_EXTRA
     import primesim_amd as P
     from primesim_amd import _abi as A
     from primesim_amd import uncore
@@ -85,7 +107,7 @@ def main() -> int:
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument("--only", default="", help="warm only the configurations whose name contains this")
     a = ap.parse_args()
-    items = [(n, bytes(c)) for n, c in configs() if a.only in n]
+    items = [(n, bytes(c), x) for n, c, x in configs() if a.only in n]
     bad = 0
     t0 = time.time()
     with ProcessPoolExecutor(a.j) as ex:
