@@ -507,6 +507,56 @@ int64_t    pu_stream_position(const pu_stream* s);
 int64_t    pu_stream_next_many(pu_stream* const* s, int count, pu_req* out, size_t n_each,
                                size_t stride, int threads);
 
+/* 0 when every record of the stream fits pu_req16, else PU_ERANGE (PU_EINVAL for
+ * parameters pu_stream_open refuses); no reference counterpart.  Decided from the
+ * parameters alone (a timer is below num_quanta*quantum, a core below num_cores, a
+ * program at most max(num_progs, 1)): it may refuse a stream that would happen to
+ * fit, and never accepts one that pu_pack_req16 would refuse. */
+int pu_stream_fits_req16(const pu_stream_params* p);
+
+/* Streams generated on the device (no reference counterpart; the first stage of a
+ * device-side ensemble: pu_dstream_next -> pu_run_device / _sliced / _pool with no
+ * request ever on the host).
+ *
+ * pu_dstream_open: `count` streams (params[i] may differ in every field, num_cores
+ * included) whose generator state lives in device memory of `device`: per stream a
+ * small header, 24 B per core, and for PU_STREAM_SHARED_UNIFORM streams 132 B per
+ * core more (the re-use ring).  Validates every params[i] (the rule of
+ * pu_stream_open) before touching a device; NULL + pu_last_error() on failure ("no
+ * HIP device" where there is none, as pu_create; PU_ENOMEM with the size asked for
+ * when the device memory cannot be had).
+ *
+ * pu_dstream_next: the next up to n_each requests of every stream: stream i writes
+ * records d_out[i*stride .. i*stride + got_i) (indices in records of the chosen
+ * format), where got_i = min(n_each, what the stream has left) and the records are
+ * exactly those that pu_stream_next would return for the same stream at the same
+ * position -- as pu_req (fmt = PU_REQ_FMT_32: all 32 bytes written, tag and padding
+ * 0) or as pu_pack_req16 of them (PU_REQ_FMT_16).  Records past got_i, and the gap
+ * between n_each and stride, are not written.  d_got (device, count uint64, may be
+ * NULL) receives got_i.  Asynchronous on hip_stream (NULL = the set's own stream);
+ * calls on one set are ordered on the host (the caller does not issue two at once),
+ * and a call on another stream than the one before runs after it on the device.
+ * stride >= n_each; d_out 16-byte aligned.  Returns 0 or PU_E*; PU_ERANGE with a
+ * message, before anything is launched, for PU_REQ_FMT_16 when a stream of the set
+ * does not pass pu_stream_fits_req16 (PU_REQ_FMT_32 still serves that set).
+ *
+ * pu_dstream_positions: requests produced so far per stream (pu_stream_position)
+ * for streams [0, n); waits for the set's outstanding calls first.
+ * pu_dstream_state_bytes: device memory the set holds.
+ *
+ * pu_dstream_positions and pu_dstream_close wait only for the work of this set (the
+ * event of its last call), never for the device (no hipDeviceSynchronize): next to
+ * another handle's resident kernel a device-wide wait lasts until that kernel idles
+ * out.  pu_dstream_close then frees the set's memory, and hipFree may itself wait
+ * for the whole device. */
+typedef struct pu_dstream pu_dstream;
+pu_dstream* pu_dstream_open(const pu_stream_params* params, int count, int device);
+void        pu_dstream_close(pu_dstream* s);
+int         pu_dstream_next(pu_dstream* s, void* d_out, size_t n_each, size_t stride, int fmt,
+                            uint64_t* d_got, void* hip_stream);
+int         pu_dstream_positions(pu_dstream* s, int64_t* out, size_t n);
+uint64_t    pu_dstream_state_bytes(const pu_dstream* s);
+
 /* Trace files ("PUTRACE1": header, thread table, pu_req records). */
 int pu_trace_write(const char* path, const pu_req* reqs, size_t n,
                    const int32_t* thread_prog, const int32_t* thread_id, int num_threads);

@@ -19,6 +19,8 @@ PU_STREAM_UNIFORM_HOTSPOT = 4
 PU_STREAM_PRODUCER_CONSUMER = 5
 PU_STREAM_UNIFORM = 6
 
+PU_REQ_FMT_32, PU_REQ_FMT_16 = 0, 1      # device request records: pu_req, pu_req16
+
 PU_ERRF_CORE_RANGE = 1 << 0
 PU_ERRF_WB_MISS = 1 << 1
 PU_ERRF_EMPTY_SHARER = 1 << 2

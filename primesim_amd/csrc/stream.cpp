@@ -36,21 +36,11 @@
 
 #include "../../include/primeuncore.h"
 #include "common.h"
+#include "stream_step.h"
+
+using namespace pu_stream_step;   // the core's step, shared with the device generator (stream_step.h)
 
 namespace {
-
-struct SplitMix64 {
-    uint64_t s;
-    uint64_t next() {
-        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    }
-};
-
-constexpr uint64_t kLine = 64;
-constexpr uint64_t kMB = 1ull << 20;
 
 struct CoreGen {
     SplitMix64 rng;
@@ -59,104 +49,9 @@ struct CoreGen {
     uint64_t recent[16] = {0};    // C2 re-use ring
     int n_recent = 0;
     int recent_head = 0;
+    uint64_t recent_get(uint64_t i) const { return recent[i]; }
+    void recent_set(int i, uint64_t a) { recent[i] = a; }
 };
-
-int default_write_pct(int kind) {
-    switch (kind) {
-        case PU_STREAM_PRIVATE_STREAMING: return 10;
-        case PU_STREAM_SHARED_UNIFORM: return 30;
-        case PU_STREAM_MULTIPROGRAM: return 20;
-        case PU_STREAM_UNIFORM_HOTSPOT: return 25;
-        case PU_STREAM_PRODUCER_CONSUMER: return 50;
-        case PU_STREAM_UNIFORM: return 25;
-        default: return -1;
-    }
-}
-
-int prog_of(const pu_stream_params* p, int core) {
-    int np = p->num_progs > 0 ? p->num_progs : 1;
-    return 1 + (int)((int64_t)core * np / p->num_cores);
-}
-
-// One request's address and type for core `c`.
-void make_request(const pu_stream_params* p, int c, CoreGen& g, int wpct,
-                  uint64_t* addr, uint8_t* type) {
-    uint64_t r0 = g.rng.next();
-    uint64_t r1 = g.rng.next();
-    uint64_t word = (r1 >> 20) & 7;  // 8-byte word within the line
-    bool wr = (int)(r1 % 100) < wpct;
-    uint64_t a = 0;
-    switch (p->kind) {
-        case PU_STREAM_PRIVATE_STREAMING: {
-            if (r0 % 100 < 5) {  // shared read-mostly table
-                a = 0x10000000ull + (r0 >> 8) % (64 * 1024 / 8) * 8;
-                wr = false;
-            } else {
-                uint64_t base = 0x100000000ull + (uint64_t)c * 16 * kMB;
-                a = base + (g.stream_pos * 8) % (2 * kMB);
-                g.stream_pos++;
-            }
-            break;
-        }
-        case PU_STREAM_SHARED_UNIFORM: {
-            if (r0 % 100 < 30 && g.n_recent > 0) {
-                a = g.recent[(r0 >> 8) % (uint64_t)g.n_recent];
-            } else {
-                a = 0x40000000ull + (r0 >> 8) % (64 * kMB / 8) * 8;
-                g.recent[g.recent_head] = a;
-                g.recent_head = (g.recent_head + 1) & 15;
-                if (g.n_recent < 16) g.n_recent++;
-            }
-            break;
-        }
-        case PU_STREAM_MULTIPROGRAM: {
-            static const uint64_t fp_mb[4] = {4, 16, 32, 64};
-            int prog = prog_of(p, c);
-            uint64_t fp = fp_mb[(prog - 1) & 3] * kMB;
-            uint64_t base = 0x80000000ull;
-            if (r0 % 100 < 50) {
-                int np = p->num_progs > 0 ? p->num_progs : 1;
-                int per = p->num_cores / np > 0 ? p->num_cores / np : 1;
-                uint64_t slice = fp / (uint64_t)per;
-                if (slice < kLine) slice = kLine;
-                uint64_t first = (uint64_t)(c % per) * slice;
-                a = base + (first + (g.stream_pos * 8) % slice) % fp;
-                g.stream_pos++;
-            } else {
-                a = base + (r0 >> 8) % (fp / 8) * 8;
-            }
-            break;
-        }
-        case PU_STREAM_UNIFORM_HOTSPOT: {
-            if (r0 % 100 < 20) {
-                a = 0x20000000ull + ((r0 >> 8) % 64) * kLine + word * 8;
-            } else {
-                a = 0x40000000ull + ((r0 >> 8) % (1ull << 20)) * kLine + word * 8;
-            }
-            break;
-        }
-        case PU_STREAM_PRODUCER_CONSUMER: {
-            int half = p->num_cores / 2 > 0 ? p->num_cores / 2 : 1;
-            int pair = c % half;
-            a = 0x100000000ull + (uint64_t)pair * 1024 * kLine + ((r0 >> 8) % 1024) * kLine + word * 8;
-            break;
-        }
-        case PU_STREAM_UNIFORM:
-        default: {
-            a = 0x40000000ull + ((r0 >> 8) % (1ull << 20)) * kLine + word * 8;
-            break;
-        }
-    }
-    *addr = a;
-    *type = wr ? PU_WR : PU_RD;
-}
-
-bool params_ok(const pu_stream_params* p) {
-    if (!p) return false;
-    if (p->kind < PU_STREAM_PRIVATE_STREAMING || p->kind > PU_STREAM_UNIFORM) return false;
-    if (p->num_cores <= 0 || p->quantum <= 0 || p->num_quanta < 0 || p->max_msg <= 0) return false;
-    return true;
-}
 
 // The generator's whole state, so a stream can be produced in consecutive
 // chunks (pu_stream_next) that concatenate to exactly pu_stream_generate's
@@ -210,7 +105,7 @@ struct StreamGen {
             k++;
             n++;
             in_msg = (in_msg + 1) % p.max_msg;
-            g.cycle += 1 + (int64_t)(g.rng.next() & 3);
+            g.cycle += gap_of(g.rng.next());
         }
         return k;
     }
@@ -245,6 +140,18 @@ int pu_stream_thread_of(const pu_stream_params* p, int core, int* prog_id, int* 
     while (first > 0 && prog_of(p, first - 1) == prog) first--;
     if (prog_id) *prog_id = prog;
     if (thread_id) *thread_id = core - first;
+    return 0;
+}
+
+// A timer is below num_quanta*quantum (a core issues only before its barrier),
+// a core below num_cores, a program at most max(num_progs, 1) (prog_of);
+// mem_type and batch_start are 0 or 1 and the tag is 0.
+int pu_stream_fits_req16(const pu_stream_params* p) {
+    if (!params_ok(p)) return pu::set_error(PU_EINVAL, "invalid stream parameters");
+    if ((int64_t)p->num_quanta * p->quantum > (int64_t)1 << 40)
+        return pu::set_error(PU_ERANGE, "stream timers (num_quanta * quantum) may pass 2^40: no pu_req16");
+    if (p->num_cores > 1 << 16) return pu::set_error(PU_ERANGE, "more than 65,536 cores: no pu_req16");
+    if ((p->num_progs > 0 ? p->num_progs : 1) > 63) return pu::set_error(PU_ERANGE, "more than 63 programs: no pu_req16");
     return 0;
 }
 

@@ -114,6 +114,13 @@ def lib() -> C.CDLL:
         "pu_msglog_close": (C.c_int, [C.c_void_p]),
         "pu_msglog_from_requests": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_int]),
+        "pu_stream_fits_req16": (C.c_int, [P(A.StreamParams)]),
+        "pu_dstream_open": (C.c_void_p, [P(A.StreamParams), C.c_int, C.c_int]),
+        "pu_dstream_close": (None, [C.c_void_p]),
+        "pu_dstream_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p,
+                                      C.c_void_p]),
+        "pu_dstream_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+        "pu_dstream_state_bytes": (C.c_uint64, [C.c_void_p]),
         "pu_trace_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]),
         "pu_alloc_core_replica": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
         "pu_dealloc_core_replica": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -272,6 +279,77 @@ class StreamSet:
         for h in self._h:
             lib().pu_stream_close(h)
         self._h = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def stream_fits_req16(spec: StreamSpec) -> bool:
+    """True when every record of the stream fits pu_req16, decided from the
+    parameters alone (pu_stream_fits_req16): never True for a stream that
+    pack_req16 would refuse."""
+    p = spec.params()
+    rc = lib().pu_stream_fits_req16(C.byref(p))
+    if rc not in (0, -34):
+        raise UncoreError(f"stream: {last_error()}")
+    return rc == 0
+
+
+class DeviceStreamSet:
+    """StreamSet on the device (pu_dstream_*): the generator state of every
+    stream lives in device memory and `next_into` writes each stream's next
+    chunk into device memory, ready for run_device / run_device_sliced /
+    run_device_pool, byte for byte what StreamSet produces.  Pointers are plain
+    integers (tensor.data_ptr()).  Needs a GPU: there is no host fallback."""
+
+    def __init__(self, specs: list[StreamSpec], device: int = 0):
+        self._h = None
+        self._n = len(specs)
+        arr = (A.StreamParams * max(1, len(specs)))(*[sp.params() for sp in specs])
+        h = lib().pu_dstream_open(arr, len(specs), device)
+        if not h:
+            raise UncoreError(f"pu_dstream_open: {last_error()}")
+        self._h = h
+
+    def _handle(self) -> int:
+        if not self._h:
+            raise UncoreError("DeviceStreamSet is closed")
+        return self._h
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def state_bytes(self) -> int:
+        """Device memory the set's generator state takes."""
+        return int(lib().pu_dstream_state_bytes(self._handle()))
+
+    def next_into(self, d_out_ptr: int, n_each: int, stride: Optional[int] = None, fmt: int = A.PU_REQ_FMT_32,
+                  d_got_ptr: int = 0, stream_ptr: int = 0) -> None:
+        """Stream i's next up to n_each requests into records [i*stride, i*stride + got_i)
+        of d_out (pu_req, or pu_req16 with fmt = PU_REQ_FMT_16); got_i goes to
+        d_got[i] (device uint64) when given.  Asynchronous on stream_ptr (a hipStream_t as an
+        integer, e.g. torch.cuda.Stream().cuda_stream); 0 is the set's own stream, which is
+        not ordered with torch's default stream: positions() waits for it."""
+        rc = lib().pu_dstream_next(self._handle(), d_out_ptr or None, n_each, n_each if stride is None else stride,
+                                   fmt, d_got_ptr or None, stream_ptr or None)
+        if rc != 0:
+            raise UncoreError(f"pu_dstream_next: {last_error()} ({rc})")
+
+    def positions(self) -> np.ndarray:
+        """Requests produced so far per stream (waits for the set's outstanding calls)."""
+        out = np.zeros(self._n, dtype=np.int64)
+        if lib().pu_dstream_positions(self._handle(), out.ctypes.data, self._n) != 0:
+            raise UncoreError(f"pu_dstream_positions: {last_error()}")
+        return out
+
+    def close(self) -> None:
+        if self._h:
+            lib().pu_dstream_close(self._h)
+            self._h = None
 
     def __del__(self):
         try:
