@@ -557,6 +557,79 @@ int         pu_dstream_next(pu_dstream* s, void* d_out, size_t n_each, size_t st
 int         pu_dstream_positions(pu_dstream* s, int64_t* out, size_t n);
 uint64_t    pu_dstream_state_bytes(const pu_dstream* s);
 
+/* Delay summaries kept on the device (no reference counterpart; the last stage of a
+ * device-side ensemble: pu_dstream_next -> pu_run_device / _sliced / _pool ->
+ * pu_dsum_add, with no request and no delay ever on the host).  Every figure is an
+ * exact integer and independent of the order of the records, so the device result
+ * equals the host fold (pu_dsum_host_add) bit for bit.
+ *
+ * The rule (primesim_amd/csrc/delay_sum_step.h):
+ *   class    0 = read, 1 = write.  pu_req16: bit 62 of b.  pu_req: 1 where mem_type ==
+ *            PU_WR, else 0 -- the engine hands mem_type on unchanged and takes its
+ *            write path only for PU_WR, so PU_RD, PU_WB and any other value are class 0.
+ *   bucket   of a delay d (int32): 0 for d <= 0, else 32 - clz(d): 1 -> 1, 2..3 -> 2,
+ *            4..7 -> 3, ..., 2^30..2^31-1 -> 31.  Bucket 0 holds the zeros that a stopped
+ *            replica's remaining range reads, the -1 of a core id out of range, and
+ *            delays that wrapped negative.
+ *   class    count, sum (exact, over every delay, non-positive ones included), min and
+ *            max (an empty class: INT32_MAX / INT32_MIN), hist[bucket].
+ *   replica  the two classes and core_out_of_range: the records whose core id is < 0 or
+ *            >= the replica's num_cores (without num_cores: < 0 only).  Such a record
+ *            still counts in its class and touches no per-core entry.
+ *   core     (optional) count and sum of the delays of the core's requests, both
+ *            classes together.
+ *
+ * pu_dsum_open: `count` replicas; num_cores NULL: no per-core tables, else `count`
+ * entries, each >= 1.  State in device memory of `device`: 568 B per replica; with
+ * tables 12 B per replica and 16 B per core more.  Arguments are validated before a device is
+ * touched; NULL + pu_last_error() on failure ("no HIP device" where there is none, PU_ENOMEM
+ * with the size asked for).
+ *
+ * pu_dsum_add: replica r folds records [d_begin[r], d_end[r]) of d_reqs (pu_req, or
+ * pu_req16 with fmt = PU_REQ_FMT_16; 16-byte aligned) and d_delay into its running
+ * summary; indices count records as in d_off / d_pos, both index arrays are in device
+ * memory with `count` entries, and d_begin[r] >= d_end[r] adds nothing.  d_off and
+ * d_off + 1 summarise a pu_run_device launch; a copy of d_pos saved before a sliced or
+ * pool launch and d_pos after it summarise exactly what that launch simulated.
+ * Asynchronous on hip_stream (NULL = the set's own stream); calls on one set are ordered
+ * on the host by the caller, and a call on another stream than the one before runs after
+ * it on the device.  Returns 0 or PU_E*.
+ *
+ * pu_dsum_read: summaries of replicas [first, first + n).  pu_dsum_read_cores: the first
+ * n (<= num_cores) per-core counts and sums of one replica (either output may be NULL);
+ * PU_EINVAL for a set opened without tables.  pu_dsum_reset: back to the state after open.
+ * pu_dsum_state_bytes: device memory the set holds.  pu_dsum_read, _read_cores, _reset and
+ * _close wait only for the work of this set (the event of its last call), never for the
+ * device, for the reason given for pu_dstream_* above.  A NULL set: PU_EINVAL, 0, no-op.
+ *
+ * pu_dsum_host_init / pu_dsum_host_add: the same fold over host arrays, for users of
+ * pu_access_batch; needs no device.  core_count / core_sum: both NULL, or num_cores (>= 1)
+ * entries each; num_cores <= 0 (tables NULL): only negative core ids are out of range. */
+#define PU_DSUM_BUCKETS 32
+typedef struct pu_dsum_class {
+    uint64_t count;
+    int64_t  sum;
+    int32_t  min, max;
+    uint64_t hist[PU_DSUM_BUCKETS];
+} pu_dsum_class;               /* 280 bytes */
+typedef struct pu_dsum_replica {
+    pu_dsum_class cls[2];
+    uint64_t core_out_of_range;
+} pu_dsum_replica;             /* 568 bytes */
+
+typedef struct pu_dsum pu_dsum;
+pu_dsum* pu_dsum_open(int count, const int32_t* num_cores, int device);
+void     pu_dsum_close(pu_dsum* s);
+int      pu_dsum_add(pu_dsum* s, const void* d_reqs, int fmt, const int32_t* d_delay,
+                     const uint64_t* d_begin, const uint64_t* d_end, void* hip_stream);
+int      pu_dsum_read(pu_dsum* s, int first, int n, pu_dsum_replica* out);
+int      pu_dsum_read_cores(pu_dsum* s, int replica, uint64_t* count_out, int64_t* sum_out, size_t n);
+int      pu_dsum_reset(pu_dsum* s);
+uint64_t pu_dsum_state_bytes(const pu_dsum* s);
+void     pu_dsum_host_init(pu_dsum_replica* acc);
+int      pu_dsum_host_add(pu_dsum_replica* acc, uint64_t* core_count, int64_t* core_sum, int num_cores,
+                          const void* reqs, int fmt, const int32_t* delays, size_t n);
+
 /* Trace files ("PUTRACE1": header, thread table, pu_req records). */
 int pu_trace_write(const char* path, const pu_req* reqs, size_t n,
                    const int32_t* thread_prog, const int32_t* thread_id, int num_threads);

@@ -21,6 +21,8 @@ PU_STREAM_UNIFORM = 6
 
 PU_REQ_FMT_32, PU_REQ_FMT_16 = 0, 1      # device request records: pu_req, pu_req16
 
+PU_DSUM_BUCKETS = 32                     # delay summaries (pu_dsum_*)
+
 PU_ERRF_CORE_RANGE = 1 << 0
 PU_ERRF_WB_MISS = 1 << 1
 PU_ERRF_EMPTY_SHARER = 1 << 2
@@ -116,6 +118,17 @@ class StreamParams(C.Structure):
     ]
 
 
+class DsumClass(C.Structure):           # pu_dsum_class
+    _fields_ = [
+        ("count", C.c_uint64), ("sum", C.c_int64), ("min", C.c_int32), ("max", C.c_int32),
+        ("hist", C.c_uint64 * PU_DSUM_BUCKETS),
+    ]
+
+
+class DsumReplica(C.Structure):         # pu_dsum_replica
+    _fields_ = [("cls", DsumClass * 2), ("core_out_of_range", C.c_uint64)]
+
+
 class ServerOpts(C.Structure):          # pu_server_opts
     _fields_ = [
         ("socket_path", C.c_char_p), ("report_prefix", C.c_char_p), ("num_sessions", C.c_int32),
@@ -141,6 +154,11 @@ REQ_DTYPE = np.dtype([
     ("mem_type", "u1"), ("batch_start", "u1"), ("tag", "<u2"), ("_pad1", "<i4"),
 ])
 assert REQ_DTYPE.itemsize == 32
+# pu_dsum_class / pu_dsum_replica as numpy structured dtypes
+DSUM_CLASS_DTYPE = np.dtype([("count", "<u8"), ("sum", "<i8"), ("min", "<i4"), ("max", "<i4"),
+                             ("hist", "<u8", (PU_DSUM_BUCKETS,))])
+DSUM_DTYPE = np.dtype([("cls", DSUM_CLASS_DTYPE, (2,)), ("core_out_of_range", "<u8")])
+assert DSUM_DTYPE.itemsize == C.sizeof(DsumReplica) == 568
 assert C.sizeof(SimCfg) == 24 + C.sizeof(SysCfg)
 
 

@@ -121,6 +121,16 @@ def lib() -> C.CDLL:
                                       C.c_void_p]),
         "pu_dstream_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
         "pu_dstream_state_bytes": (C.c_uint64, [C.c_void_p]),
+        "pu_dsum_open": (C.c_void_p, [C.c_int, P(C.c_int32), C.c_int]),
+        "pu_dsum_close": (None, [C.c_void_p]),
+        "pu_dsum_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "pu_dsum_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(A.DsumReplica)]),
+        "pu_dsum_read_cores": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64), P(C.c_int64), C.c_size_t]),
+        "pu_dsum_reset": (C.c_int, [C.c_void_p]),
+        "pu_dsum_state_bytes": (C.c_uint64, [C.c_void_p]),
+        "pu_dsum_host_init": (None, [P(A.DsumReplica)]),
+        "pu_dsum_host_add": (C.c_int, [P(A.DsumReplica), P(C.c_uint64), P(C.c_int64), C.c_int, C.c_void_p, C.c_int,
+                                       P(C.c_int32), C.c_size_t]),
         "pu_trace_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]),
         "pu_alloc_core_replica": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
         "pu_dealloc_core_replica": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -349,6 +359,119 @@ class DeviceStreamSet:
     def close(self) -> None:
         if self._h:
             lib().pu_dstream_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------- delay summaries
+def _as(a: np.ndarray, ctype):
+    return a.ctypes.data_as(C.POINTER(ctype))
+
+
+def summarize_delays(reqs: np.ndarray, delays: np.ndarray, num_cores: Optional[int] = None,
+                     fmt: int = A.PU_REQ_FMT_32):
+    """The host fold of (request, delay) pairs (pu_dsum_host_add; the rule is in
+    include/primeuncore.h): returns (summary, core_count, core_sum), where summary is
+    one A.DSUM_DTYPE record and the per-core arrays (num_cores entries) are None
+    without num_cores.  reqs: REQ_DTYPE records, or with fmt = PU_REQ_FMT_16 the
+    [n, 2] uint64 array of pack_req16.  Needs no device."""
+    n = len(delays)
+    if fmt == A.PU_REQ_FMT_16:
+        assert reqs.dtype == np.uint64 and reqs.shape == (n, 2)
+    else:
+        assert reqs.dtype == A.REQ_DTYPE and reqs.shape == (n,)
+    reqs = np.ascontiguousarray(reqs)
+    delays = np.ascontiguousarray(delays, dtype=np.int32)
+    out = np.zeros(1, dtype=A.DSUM_DTYPE)
+    lib().pu_dsum_host_init(_as(out, A.DsumReplica))
+    cnt = sm = None
+    if num_cores is not None:
+        # (at least one entry, so that the library sees tables and refuses a num_cores below 1)
+        cnt, sm = np.zeros(max(num_cores, 1), dtype=np.uint64), np.zeros(max(num_cores, 1), dtype=np.int64)
+    rc = lib().pu_dsum_host_add(_as(out, A.DsumReplica), None if cnt is None else _as(cnt, C.c_uint64),
+                                None if sm is None else _as(sm, C.c_int64), 0 if num_cores is None else num_cores,
+                                reqs.ctypes.data, fmt, _as(delays, C.c_int32), n)
+    if rc != 0:
+        raise UncoreError(f"pu_dsum_host_add: {last_error()} ({rc})")
+    return out[0], cnt, sm
+
+
+class DeviceDelaySummary:
+    """Per-replica delay summaries kept on the device (pu_dsum_*): `add` folds every
+    replica's records [begin[r], end[r]) of device request and delay arrays into its
+    running summary, bit for bit what summarize_delays gives.  num_cores (one entry per
+    replica) adds per-core (count, sum) tables.  Pointers are plain integers
+    (tensor.data_ptr()).  Needs a GPU: there is no host fallback."""
+
+    def __init__(self, count: int, num_cores=None, device: int = 0):
+        self._h = None
+        self._n = count
+        self._nc = None
+        arr = None
+        if num_cores is not None:
+            self._nc = [int(c) for c in num_cores]
+            if len(self._nc) != count:
+                raise UncoreError(f"DeviceDelaySummary: {len(self._nc)} num_cores entries for {count} replicas")
+            arr = (C.c_int32 * max(1, count))(*self._nc)
+        h = lib().pu_dsum_open(count, arr, device)
+        if not h:
+            raise UncoreError(f"pu_dsum_open: {last_error()}")
+        self._h = h
+
+    def _handle(self) -> int:
+        if not self._h:
+            raise UncoreError("DeviceDelaySummary is closed")
+        return self._h
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def state_bytes(self) -> int:
+        """Device memory the set holds."""
+        return int(lib().pu_dsum_state_bytes(self._handle()))
+
+    def add(self, d_reqs_ptr: int, d_delay_ptr: int, d_begin_ptr: int, d_end_ptr: int, fmt: int = A.PU_REQ_FMT_32,
+            stream_ptr: int = 0) -> None:
+        """Asynchronous on stream_ptr (a hipStream_t as an integer); 0 is the set's own
+        stream, which is not ordered with torch's streams.  d_begin / d_end: device uint64,
+        one entry per replica, in records (d_off and d_off + 1 after run_device)."""
+        rc = lib().pu_dsum_add(self._handle(), d_reqs_ptr or None, fmt, d_delay_ptr or None, d_begin_ptr or None,
+                               d_end_ptr or None, stream_ptr or None)
+        if rc != 0:
+            raise UncoreError(f"pu_dsum_add: {last_error()} ({rc})")
+
+    def read(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Summaries of replicas [first, first + n) as A.DSUM_DTYPE records (waits for the set's calls)."""
+        n = self._n - first if n is None else n
+        out = np.zeros(max(n, 0), dtype=A.DSUM_DTYPE)
+        rc = lib().pu_dsum_read(self._handle(), first, n, _as(out, A.DsumReplica))
+        if rc != 0:
+            raise UncoreError(f"pu_dsum_read: {last_error()} ({rc})")
+        return out
+
+    def cores(self, replica: int) -> tuple[np.ndarray, np.ndarray]:
+        """(count, sum) per core of one replica; raises for a set opened without num_cores."""
+        nc = self._nc[replica] if self._nc is not None and 0 <= replica < self._n else 0
+        cnt, sm = np.zeros(nc, dtype=np.uint64), np.zeros(nc, dtype=np.int64)
+        rc = lib().pu_dsum_read_cores(self._handle(), replica, _as(cnt, C.c_uint64), _as(sm, C.c_int64), nc)
+        if rc != 0:
+            raise UncoreError(f"pu_dsum_read_cores: {last_error()} ({rc})")
+        return cnt, sm
+
+    def reset(self) -> None:
+        rc = lib().pu_dsum_reset(self._handle())
+        if rc != 0:
+            raise UncoreError(f"pu_dsum_reset: {last_error()} ({rc})")
+
+    def close(self) -> None:
+        if self._h:
+            lib().pu_dsum_close(self._h)
             self._h = None
 
     def __del__(self):

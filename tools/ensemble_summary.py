@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""An ensemble of independent simulations that never leaves the device: per chunk
+DeviceStreamSet.next_into -> UncoreManager.run_device -> DeviceDelaySummary.add, all
+on one torch stream.  No request and no delay is copied to the host; the only
+device-to-host traffic is the summaries (568 B per replica) and the error flags.
+
+Prints one JSON line per replica: requests, mean read and write latency, the upper
+bounds of the histogram buckets that hold the median and the 99th percentile of each
+class (a bucket b > 0 holds delays 2^(b-1) .. 2^b - 1; bucket 0 holds delays <= 0),
+cores out of range and the engine's error flags.  Needs a GPU: there is no CPU fallback.
+
+  python tools/ensemble_summary.py --preset C1 --kind 1 --replicas 4 --chunk 2000 --chunks 2
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def bucket_upper(b: int) -> int:
+    """The largest delay of bucket b (0 for the bucket of the non-positive delays)."""
+    return 0 if b == 0 else (1 << b) - 1
+
+
+def percentile_bound(hist, pct: int):
+    """Upper bound of the first bucket at which the running count reaches pct percent; None for an empty class."""
+    total = int(hist.sum())
+    if total == 0:
+        return None
+    need, run = -(-total * pct // 100), 0
+    for b, h in enumerate(hist):
+        run += int(h)
+        if run >= need:
+            return bucket_upper(b)
+    return bucket_upper(len(hist) - 1)
+
+
+def replica_line(r: int, seed: int, s, flags: int) -> dict:
+    line = {"replica": r, "seed": seed, "requests": int(s["cls"]["count"].sum())}
+    for c, name in enumerate(("read", "write")):
+        k = s["cls"][c]
+        n = int(k["count"])
+        line[name] = {"count": n, "sum": int(k["sum"]), "mean": int(k["sum"]) / n if n else None,
+                      "min": int(k["min"]) if n else None, "max": int(k["max"]) if n else None,
+                      "p50_le": percentile_bound(k["hist"], 50), "p99_le": percentile_bound(k["hist"], 99)}
+    line["core_out_of_range"] = int(s["core_out_of_range"])
+    line["error_flags"] = flags
+    return line
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    g = ap.add_mutually_exclusive_group()
+    g.add_argument("--preset", default="C1", help="C1 .. C5 (primesim_amd.config.preset)")
+    g.add_argument("--xml", help="a config_prime XML file instead of a preset")
+    ap.add_argument("--kind", type=int, default=4, help="PU_STREAM_* kind of the synthetic streams (1 .. 6)")
+    ap.add_argument("--replicas", type=int, default=4)
+    ap.add_argument("--chunk", type=int, default=2000, help="requests per replica and chunk")
+    ap.add_argument("--chunks", type=int, default=2)
+    ap.add_argument("--seed-base", type=int, default=1, help="replica r streams with seed seed-base + r")
+    ap.add_argument("--fmt", type=int, choices=(32, 16), default=32, help="device request records: pu_req or pu_req16")
+    args = ap.parse_args()
+
+    import torch
+
+    import primesim_amd as P
+    from primesim_amd import _abi as A
+    from primesim_amd import config as CF
+
+    if not torch.cuda.is_available():
+        print("ensemble_summary: no GPU (the device pipeline has no CPU fallback)", file=sys.stderr)
+        return 2
+    cfg = P.load_config(args.xml) if args.xml else P.config_from_dict(CF.preset(args.preset))
+    R, n, nc = args.replicas, args.chunk, cfg.sys.num_cores
+    fmt, rec = (A.PU_REQ_FMT_16, 16) if args.fmt == 16 else (A.PU_REQ_FMT_32, 32)
+    quantum = cfg.thread_sync_interval
+    # a core issues at least quantum / 4 requests a quantum: enough quanta for every chunk
+    quanta = -(-n * args.chunks * 4 // (nc * quantum)) + 1
+    specs = [P.StreamSpec(args.kind, nc, seed=args.seed_base + r, quantum=quantum, num_quanta=quanta,
+                          max_msg=cfg.max_msg_size) for r in range(R)]
+
+    dev = torch.device("cuda", 0)
+    d_reqs = torch.empty((R, n, rec), dtype=torch.uint8, device=dev)
+    d_del = torch.empty((R, n), dtype=torch.int32, device=dev)
+    d_off = torch.arange(R + 1, dtype=torch.int64, device=dev) * n      # replica r owns records [r*n, (r+1)*n)
+    torch.cuda.synchronize(dev)
+    stream = torch.cuda.Stream(dev)                                     # one stream orders the three stages
+    sp = stream.cuda_stream
+
+    um = P.UncoreManager()
+    um.init(cfg, replicas=R)
+    dss = P.DeviceStreamSet(specs)
+    dsum = P.DeviceDelaySummary(R, num_cores=[nc] * R)
+    try:
+        for prog, th in P.stream_threads(specs[0]):
+            um.allocCore(prog, th)
+        um.set_device_req_format(fmt)
+        for _ in range(args.chunks):
+            dss.next_into(d_reqs.data_ptr(), n, fmt=fmt, stream_ptr=sp)
+            um.run_device(d_reqs.data_ptr(), d_off.data_ptr(), d_del.data_ptr(), sp)
+            dsum.add(d_reqs.data_ptr(), d_del.data_ptr(), d_off.data_ptr(), d_off.data_ptr() + 8, fmt=fmt, stream_ptr=sp)
+        summaries = dsum.read()                                         # waits for the last add
+        stream.synchronize()
+        if int(dss.positions().min()) != n * args.chunks:
+            print("ensemble_summary: a stream ended before its last chunk", file=sys.stderr)
+            return 1
+        flags = um.error_flags(R)
+    finally:
+        dsum.close()
+        dss.close()
+        um.close()
+    for r in range(R):
+        print(json.dumps(replica_line(r, args.seed_base + r, summaries[r], int(flags[r]))))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
