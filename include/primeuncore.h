@@ -159,6 +159,9 @@ typedef struct pu_req {
  *   a = addr_dmem
  *   b = timer (bits 0-39) | core (40-55) | prog_id (56-61) | mem_type (62)
  *       | batch_start (63);  tag is 0.
+ * The PU_REQ16_* constants below are that layout: PU_REQ16_B packs b from
+ * fields that fit and PU_REQ16_TIMER / _CORE / _PROG / _TYPE / _BATCH take
+ * them out again.  Every packer and reader of the library goes through them.
  * pu_pack_req16 packs n records and returns 0, or PU_ERANGE (out untouched
  * past the record it names in the error text) at the first that does not
  * fit: timer outside [0, 2^40), core outside [0, 2^16), prog_id outside
@@ -172,6 +175,24 @@ typedef struct pu_req {
 typedef struct pu_req16 {
     uint64_t a, b;
 } pu_req16;
+#define PU_REQ16_TIMER_BITS 40
+#define PU_REQ16_CORE_SHIFT 40
+#define PU_REQ16_CORE_BITS 16
+#define PU_REQ16_PROG_SHIFT 56
+#define PU_REQ16_PROG_BITS 6
+#define PU_REQ16_TYPE_SHIFT 62
+#define PU_REQ16_BATCH_SHIFT 63
+#define PU_REQ16_B(timer, core, prog_id, mem_type, batch_start)               \
+    ((uint64_t)(timer) | (uint64_t)(uint32_t)(core) << PU_REQ16_CORE_SHIFT |  \
+     (uint64_t)(uint32_t)(prog_id) << PU_REQ16_PROG_SHIFT |                   \
+     (uint64_t)(mem_type) << PU_REQ16_TYPE_SHIFT | (uint64_t)(batch_start) << PU_REQ16_BATCH_SHIFT)
+#define PU_REQ16_TIMER(b) ((int64_t)((uint64_t)(b) & (((uint64_t)1 << PU_REQ16_TIMER_BITS) - 1)))
+#define PU_REQ16_CORE(b) \
+    ((int32_t)(((uint64_t)(b) >> PU_REQ16_CORE_SHIFT) & (((uint64_t)1 << PU_REQ16_CORE_BITS) - 1)))
+#define PU_REQ16_PROG(b) \
+    ((int32_t)(((uint64_t)(b) >> PU_REQ16_PROG_SHIFT) & (((uint64_t)1 << PU_REQ16_PROG_BITS) - 1)))
+#define PU_REQ16_TYPE(b) ((uint8_t)(((uint64_t)(b) >> PU_REQ16_TYPE_SHIFT) & 1u))
+#define PU_REQ16_BATCH(b) ((uint8_t)((uint64_t)(b) >> PU_REQ16_BATCH_SHIFT))
 #define PU_REQ_FMT_32 0
 #define PU_REQ_FMT_16 1
 

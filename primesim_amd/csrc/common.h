@@ -13,6 +13,12 @@ namespace pu {
 // Records a message for pu_last_error() and returns `code`.
 int set_error(int code, const std::string& msg);
 
+// 0 when `device` is a HIP device of this machine, else PU_ENODEV with the
+// error "no HIP device available", followed by " (note)" where a note is given.
+int device_check(int device, const char* note = nullptr);
+
+inline bool req_fmt_ok(int fmt) { return fmt == PU_REQ_FMT_32 || fmt == PU_REQ_FMT_16; }
+
 // pu_run_device with extra kernel flags (PU_KF_*, geometry.h): the server's
 // per-receive-thread stop.  use_replay_mode = false launches open-loop whatever
 // pu_set_replay_mode left on the handle (live clients' timers are real).

@@ -40,15 +40,16 @@
 
 #include <cstddef>
 #include <cstdint>
-#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/primeuncore.h"
 #include "common.h"
 #include "delay_sum_step.h"
+#include "device_set.h"
 
 using namespace pu_delay_sum;
+using pu::round16;
 
 namespace {
 
@@ -257,25 +258,14 @@ __global__ __launch_bounds__(kThreads) void dsum_add_kernel(pu_dsum_replica* rep
     }
 }
 
-size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-bool fmt_ok(int fmt) { return fmt == PU_REQ_FMT_32 || fmt == PU_REQ_FMT_16; }
-
 }  // namespace
 
-struct pu_dsum {
-    int device = 0;
+struct pu_dsum : pu::DeviceSet {
     int count = 0;
     bool cores = false;
     std::vector<int32_t> nc;        // per replica (with tables)
     std::vector<uint64_t> core0;    // a replica's first element in the per-core arrays
     size_t lds_bytes = 0;           // dynamic LDS of a launch
-    hipStream_t stream = nullptr;   // the set's own stream
-    hipStream_t last = nullptr;     // the stream of the last call
-    hipEvent_t ev = nullptr;        // recorded after every call: the set's outstanding work
-    bool ev_recorded = false;
-    uint8_t* base = nullptr;
-    size_t bytes = 0;
     pu_dsum_replica* rep = nullptr;
     int32_t* d_nc = nullptr;
     uint64_t* d_core0 = nullptr;
@@ -285,43 +275,12 @@ struct pu_dsum {
 
 namespace {
 
-// Waits for the set's outstanding calls only: the event of its last launch
-// (every launch on another stream first waits for the one before it).
-int wait_outstanding(pu_dsum* s) {
-    if (s->ev_recorded && hipEventSynchronize(s->ev) != hipSuccess)
-        return pu::set_error(PU_EIO, "waiting for the summary set's outstanding calls failed");
-    return 0;
-}
-
-void release(pu_dsum* s) {
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    if (s->base) (void)hipFree(s->base);
-    if (s->ev) (void)hipEventDestroy(s->ev);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
-}
-
-// The launch is ordered after the set's last call and becomes its last call.
-int order_before(pu_dsum* s, hipStream_t st) {
-    if (st != s->last && s->ev_recorded && hipStreamWaitEvent(st, s->ev, 0) != hipSuccess)
-        return pu::set_error(PU_EIO, "ordering the call after the set's last call failed");
-    return 0;
-}
-int record_after(pu_dsum* s, hipStream_t st, const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pu::set_error(PU_EIO, std::string(what) + ": launch failed: " + hipGetErrorString(e));
-    if (hipEventRecord(s->ev, st) != hipSuccess) return pu::set_error(PU_EIO, "event record failed");
-    s->ev_recorded = true;
-    s->last = st;
-    return 0;
-}
-
 int launch_reset(pu_dsum* s) {
-    int rc = order_before(s, s->stream);
+    int rc = s->order_before(s->stream);
     if (rc) return rc;
     hipLaunchKernelGGL(dsum_reset_kernel, dim3((unsigned)s->count), dim3(kThreads), 0, s->stream, s->rep, s->d_nc,
                        s->d_core0, s->g_cnt, s->g_sum);
-    return record_after(s, s->stream, "pu_dsum_reset");
+    return s->record_after(s->stream, "pu_dsum_reset");
 }
 
 template <int FMT, bool CORES>
@@ -346,23 +305,10 @@ pu_dsum* pu_dsum_open(int count, const int32_t* num_cores, int device) {
                 pu::set_error(PU_EINVAL, "pu_dsum_open: invalid num_cores (replica " + std::to_string(i) + ")");
                 return nullptr;
             }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        pu::set_error(PU_ENODEV, "no HIP device available (the device summaries have no CPU fallback; "
-                                 "pu_dsum_host_add folds host arrays)");
+    if (pu::device_check(device, "the device summaries have no CPU fallback; pu_dsum_host_add folds host arrays") != 0)
         return nullptr;
-    }
-    pu_dsum* s = new (std::nothrow) pu_dsum;
-    if (!s) {
-        pu::set_error(PU_ENOMEM, "out of host memory");
-        return nullptr;
-    }
-    auto fail = [&](int code, const std::string& msg) -> pu_dsum* {
-        release(s);
-        pu::set_error(code, msg);
-        return nullptr;
-    };
-    s->device = device;
+    pu_dsum* s = pu::new_set<pu_dsum>();
+    if (!s) return nullptr;
     s->count = count;
     s->cores = num_cores != nullptr;
 
@@ -382,19 +328,10 @@ pu_dsum* pu_dsum_open(int count, const int32_t* num_cores, int device) {
     const size_t off_c0 = off_nc + (s->cores ? round16((size_t)count * 4) : 0);
     const size_t off_cnt = off_c0 + (s->cores ? round16((size_t)count * 8) : 0);
     const size_t off_sum = off_cnt + round16(cores * 8);
-    s->bytes = off_sum + round16(cores * 8);
 
-    if (hipSetDevice(device) != hipSuccess) return fail(PU_ENODEV, "hipSetDevice failed");
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return fail(PU_EIO, "stream create failed");
-    if (hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) return fail(PU_EIO, "event create failed");
-    void* p = nullptr;
-    if (hipMalloc(&p, s->bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(PU_ENOMEM, "pu_dsum_open: " + std::to_string(s->bytes) + " bytes of device memory for the summaries of " +
-                                   std::to_string(count) + " replicas (" + std::to_string(cores) +
-                                   " cores) could not be allocated");
-    }
-    s->base = (uint8_t*)p;
+    if (s->open(device, off_sum + round16(cores * 8), "pu_dsum_open: the summaries of " + std::to_string(count) +
+                                                          " replicas (" + std::to_string(cores) + " cores)") != 0)
+        return pu::drop_set(s);
     s->rep = (pu_dsum_replica*)s->base;
     if (s->cores) {
         s->d_nc = (int32_t*)(s->base + off_nc);
@@ -404,28 +341,23 @@ pu_dsum* pu_dsum_open(int count, const int32_t* num_cores, int device) {
         // from the set's own vectors, which live as long as the set
         if (hipMemcpyAsync(s->d_nc, s->nc.data(), (size_t)count * 4, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
             hipMemcpyAsync(s->d_core0, s->core0.data(), (size_t)count * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess)
-            return fail(PU_EIO, "table layout upload failed");
+            return pu::drop_set(s, PU_EIO, "table layout upload failed");
     }
-    if (launch_reset(s) != 0) return fail(PU_EIO, pu_last_error());
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return fail(PU_EIO, "state initialisation failed");
+    if (launch_reset(s) != 0) return pu::drop_set(s);
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return pu::drop_set(s, PU_EIO, "state initialisation failed");
     return s;
 }
 
-void pu_dsum_close(pu_dsum* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    (void)wait_outstanding(s);
-    release(s);
-}
+void pu_dsum_close(pu_dsum* s) { pu::close_set(s); }
 
 int pu_dsum_add(pu_dsum* s, const void* d_reqs, int fmt, const int32_t* d_delay, const uint64_t* d_begin,
                 const uint64_t* d_end, void* hip_stream) {
-    if (!s || !fmt_ok(fmt) || !d_reqs || !d_delay || !d_begin || !d_end || ((uintptr_t)d_reqs & 15))
+    if (!s || !pu::req_fmt_ok(fmt) || !d_reqs || !d_delay || !d_begin || !d_end || ((uintptr_t)d_reqs & 15))
         return pu::set_error(PU_EINVAL, "pu_dsum_add: bad arguments");
-    if (hipSetDevice(s->device) != hipSuccess) return pu::set_error(PU_ENODEV, "hipSetDevice failed");
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : s->stream;
-    // the state is the set's: a call on another stream runs after the call before it
-    int rc = order_before(s, st);
+    int rc = s->use();
+    if (rc) return rc;
+    hipStream_t st = s->pick(hip_stream);
+    rc = s->order_before(st);
     if (rc) return rc;
     if (fmt == PU_REQ_FMT_16) {
         if (s->cores)
@@ -438,22 +370,19 @@ int pu_dsum_add(pu_dsum* s, const void* d_reqs, int fmt, const int32_t* d_delay,
         else
             launch_add<PU_REQ_FMT_32, false>(s, st, d_reqs, d_delay, d_begin, d_end);
     }
-    return record_after(s, st, "pu_dsum_add");
+    return s->record_after(st, "pu_dsum_add");
 }
 
 int pu_dsum_read(pu_dsum* s, int first, int n, pu_dsum_replica* out) {
     if (!s || first < 0 || n < 0 || (!out && n)) return pu::set_error(PU_EINVAL, "pu_dsum_read: bad arguments");
     if ((int64_t)first + n > s->count) return pu::set_error(PU_ERANGE, "more replicas than the set holds");
     if (n == 0) return 0;
-    if (hipSetDevice(s->device) != hipSuccess) return pu::set_error(PU_ENODEV, "hipSetDevice failed");
-    int rc = wait_outstanding(s);
-    if (rc) return rc;
-    // on the set's own (non-blocking) stream: a copy on the null stream would wait for every blocking stream
-    if (hipMemcpyAsync(out, s->rep + first, (size_t)n * sizeof(pu_dsum_replica), hipMemcpyDeviceToHost, s->stream) !=
-            hipSuccess ||
-        hipStreamSynchronize(s->stream) != hipSuccess)
-        return pu::set_error(PU_EIO, "reading the summaries failed");
-    return 0;
+    return s->read_back(
+        [&](hipStream_t st) {
+            return hipMemcpyAsync(out, s->rep + first, (size_t)n * sizeof(pu_dsum_replica), hipMemcpyDeviceToHost, st) ==
+                   hipSuccess;
+        },
+        "reading the summaries failed");
 }
 
 int pu_dsum_read_cores(pu_dsum* s, int replica, uint64_t* count_out, int64_t* sum_out, size_t n) {
@@ -462,21 +391,19 @@ int pu_dsum_read_cores(pu_dsum* s, int replica, uint64_t* count_out, int64_t* su
     if (replica >= s->count) return pu::set_error(PU_ERANGE, "more replicas than the set holds");
     if (n > (size_t)s->nc[(size_t)replica]) return pu::set_error(PU_ERANGE, "more cores than the replica has");
     if (n == 0 || (!count_out && !sum_out)) return 0;
-    if (hipSetDevice(s->device) != hipSuccess) return pu::set_error(PU_ENODEV, "hipSetDevice failed");
-    int rc = wait_outstanding(s);
-    if (rc) return rc;
     const uint64_t c0 = s->core0[(size_t)replica];
-    if ((count_out && hipMemcpyAsync(count_out, s->g_cnt + c0, n * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-        (sum_out && hipMemcpyAsync(sum_out, s->g_sum + c0, n * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-        hipStreamSynchronize(s->stream) != hipSuccess)
-        return pu::set_error(PU_EIO, "reading the per-core tables failed");
-    return 0;
+    return s->read_back(
+        [&](hipStream_t st) {
+            return (!count_out || hipMemcpyAsync(count_out, s->g_cnt + c0, n * 8, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+                   (!sum_out || hipMemcpyAsync(sum_out, s->g_sum + c0, n * 8, hipMemcpyDeviceToHost, st) == hipSuccess);
+        },
+        "reading the per-core tables failed");
 }
 
 int pu_dsum_reset(pu_dsum* s) {
     if (!s) return pu::set_error(PU_EINVAL, "pu_dsum_reset: no set");
-    if (hipSetDevice(s->device) != hipSuccess) return pu::set_error(PU_ENODEV, "hipSetDevice failed");
-    return launch_reset(s);   // on the set's own stream, after the set's last call
+    int rc = s->use();
+    return rc ? rc : launch_reset(s);   // on the set's own stream, after the set's last call
 }
 
 uint64_t pu_dsum_state_bytes(const pu_dsum* s) { return s ? (uint64_t)s->bytes : 0; }
@@ -487,7 +414,7 @@ void pu_dsum_host_init(pu_dsum_replica* acc) {
 
 int pu_dsum_host_add(pu_dsum_replica* acc, uint64_t* core_count, int64_t* core_sum, int num_cores, const void* reqs,
                      int fmt, const int32_t* delays, size_t n) {
-    if (!acc || !fmt_ok(fmt) || (n && (!reqs || !delays)) || !core_count != !core_sum || (core_count && num_cores < 1))
+    if (!acc || !pu::req_fmt_ok(fmt) || (n && (!reqs || !delays)) || !core_count != !core_sum || (core_count && num_cores < 1))
         return pu::set_error(PU_EINVAL, "pu_dsum_host_add: bad arguments");
     const uint32_t limit = core_limit(num_cores);
     const pu_req* r32 = (const pu_req*)reqs;

@@ -11,27 +11,17 @@
 #include <cstdint>
 
 #include "../../include/primeuncore.h"
-
-#if defined(__HIP__) || defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#ifndef PU_HD
-#define PU_HD __host__ __device__
-#endif
-#else
-#ifndef PU_HD
-#define PU_HD
-#endif
-#endif
+#include "pu_hd.h"
 
 namespace pu_delay_sum {
 
 // Class 0 is a read, class 1 a write.  The engine passes pu_req.mem_type on
 // unchanged as Req.type (engine.hip: replica_steps) and takes the write path
 // only where that equals PU_WR; PU_RD, PU_WB and every other value go the other
-// way.  pu_req16 carries one bit of it (bit 62 of b).
+// way.  pu_req16 carries one bit of it (PU_REQ16_TYPE).
 PU_HD inline int class_of_mem_type(uint32_t mem_type) { return mem_type == (uint32_t)PU_WR ? 1 : 0; }
-PU_HD inline int class_of_req16_b(uint64_t b) { return (int)((b >> 62) & 1u); }
-PU_HD inline int32_t core_of_req16_b(uint64_t b) { return (int32_t)((b >> 40) & 0xFFFFu); }
+PU_HD inline int class_of_req16_b(uint64_t b) { return PU_REQ16_TYPE(b); }
+PU_HD inline int32_t core_of_req16_b(uint64_t b) { return PU_REQ16_CORE(b); }
 
 // Without a core count only a negative id is out of range.
 constexpr uint32_t kNoCoreLimit = 0x80000000u;

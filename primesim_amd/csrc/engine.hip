@@ -2823,17 +2823,17 @@ __device__ __forceinline__ void hdr_image_out(char* qhdr, uint32_t nqueues, uint
     for (uint32_t k = t; k < nqueues * PU_LDS_SLOT; k += 128) gh[k] = lds_qhdr[k];
 }
 
-// A 16-B request record (pu_req16, primeuncore.h): a = addr_dmem; b = timer
-// (bits 0-39) | core (40-55) | prog_id (56-61) | mem_type (62) | batch_start
-// (63); tag 0.  pu_pack_req16 refuses what does not fit, so this is exact.
+// A 16-B request record (pu_req16, primeuncore.h): a = addr_dmem; b = the
+// fields of PU_REQ16_B; tag 0.  pu_pack_req16 refuses what does not fit, so
+// this is exact.
 __device__ __forceinline__ pu_req req_unpack16(v2u64 w) {
     pu_req q;
     q.addr = w.x;
-    q.timer = (int64_t)(w.y & ((1ull << 40) - 1));
-    q.core = (int32_t)((w.y >> 40) & 0xFFFFu);
-    q.prog_id = (int32_t)((w.y >> 56) & 63u);
-    q.mem_type = (uint8_t)((w.y >> 62) & 1u);
-    q.batch_start = (uint8_t)(w.y >> 63);
+    q.timer = PU_REQ16_TIMER(w.y);
+    q.core = PU_REQ16_CORE(w.y);
+    q.prog_id = PU_REQ16_PROG(w.y);
+    q.mem_type = PU_REQ16_TYPE(w.y);
+    q.batch_start = PU_REQ16_BATCH(w.y);
     q.tag = 0;
     q._pad1 = 0;
     return q;

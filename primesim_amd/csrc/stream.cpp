@@ -148,10 +148,11 @@ int pu_stream_thread_of(const pu_stream_params* p, int core, int* prog_id, int* 
 // mem_type and batch_start are 0 or 1 and the tag is 0.
 int pu_stream_fits_req16(const pu_stream_params* p) {
     if (!params_ok(p)) return pu::set_error(PU_EINVAL, "invalid stream parameters");
-    if ((int64_t)p->num_quanta * p->quantum > (int64_t)1 << 40)
+    if ((int64_t)p->num_quanta * p->quantum > (int64_t)1 << PU_REQ16_TIMER_BITS)
         return pu::set_error(PU_ERANGE, "stream timers (num_quanta * quantum) may pass 2^40: no pu_req16");
-    if (p->num_cores > 1 << 16) return pu::set_error(PU_ERANGE, "more than 65,536 cores: no pu_req16");
-    if ((p->num_progs > 0 ? p->num_progs : 1) > 63) return pu::set_error(PU_ERANGE, "more than 63 programs: no pu_req16");
+    if (p->num_cores > 1 << PU_REQ16_CORE_BITS) return pu::set_error(PU_ERANGE, "more than 65,536 cores: no pu_req16");
+    if ((p->num_progs > 0 ? p->num_progs : 1) >= 1 << PU_REQ16_PROG_BITS)   // prog_of's largest value must fit the field
+        return pu::set_error(PU_ERANGE, "more than 63 programs: no pu_req16");
     return 0;
 }
 

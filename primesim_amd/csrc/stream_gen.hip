@@ -34,15 +34,16 @@
 
 #include <cstddef>
 #include <cstdint>
-#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/primeuncore.h"
 #include "common.h"
+#include "device_set.h"
 #include "stream_step.h"
 
 using namespace pu_stream_step;
+using pu::round16;
 
 namespace {
 
@@ -80,8 +81,7 @@ __device__ __forceinline__ void store_record(void* out, size_t idx, uint64_t add
     if (FMT == PU_REQ_FMT_16) {
         u64x2 v;
         v.x = addr;
-        v.y = (uint64_t)timer | (uint64_t)(uint32_t)core << 40 | (uint64_t)(uint32_t)prog << 56 |
-              (uint64_t)type << 62 | (uint64_t)batch_start << 63;
+        v.y = PU_REQ16_B(timer, core, prog, type, batch_start);
         ((u64x2*)out)[idx] = v;
     } else {   // pu_req: addr, timer | core, prog_id | mem_type, batch_start, tag = 0, _pad1 = 0
         u64x2 lo, hi;
@@ -222,45 +222,16 @@ __global__ __launch_bounds__(kThreads) void dstream_next_kernel(DsHdr* hdrs, uin
     }
 }
 
-size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 }  // namespace
 
-struct pu_dstream {
-    int device = 0;
+struct pu_dstream : pu::DeviceSet {
     int count = 0;
-    std::string refuse16;        // why the set has no format 16 ("" = every stream fits)
-    hipStream_t stream = nullptr;   // the set's own stream
-    hipStream_t last = nullptr;     // the stream of the last call
-    hipEvent_t ev = nullptr;        // recorded after every call: the set's outstanding work
-    bool ev_recorded = false;
-    uint8_t* base = nullptr;
-    size_t bytes = 0;
+    std::string refuse16;   // why the set has no format 16 ("" = every stream fits)
     DsHdr* hdrs = nullptr;
     uint64_t* rng = nullptr;
     int64_t* cyc = nullptr;
     uint64_t* spos = nullptr;
 };
-
-namespace {
-
-// Waits for the set's outstanding calls only: the event of its last launch
-// (every launch on another stream first waits for the one before it).
-int wait_outstanding(pu_dstream* s) {
-    if (s->ev_recorded && hipEventSynchronize(s->ev) != hipSuccess)
-        return pu::set_error(PU_EIO, "waiting for the stream set's outstanding calls failed");
-    return 0;
-}
-
-void release(pu_dstream* s) {
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    if (s->base) (void)hipFree(s->base);
-    if (s->ev) (void)hipEventDestroy(s->ev);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -274,22 +245,9 @@ pu_dstream* pu_dstream_open(const pu_stream_params* params, int count, int devic
             pu::set_error(PU_EINVAL, "pu_dstream_open: invalid stream parameters (stream " + std::to_string(i) + ")");
             return nullptr;
         }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        pu::set_error(PU_ENODEV, "no HIP device available (the device generator has no CPU fallback)");
-        return nullptr;
-    }
-    pu_dstream* s = new (std::nothrow) pu_dstream;
-    if (!s) {
-        pu::set_error(PU_ENOMEM, "out of host memory");
-        return nullptr;
-    }
-    auto fail = [&](int code, const std::string& msg) -> pu_dstream* {
-        release(s);
-        pu::set_error(code, msg);
-        return nullptr;
-    };
-    s->device = device;
+    if (pu::device_check(device, "the device generator has no CPU fallback") != 0) return nullptr;
+    pu_dstream* s = pu::new_set<pu_dstream>();
+    if (!s) return nullptr;
     s->count = count;
 
     // layout: headers | rng | cycle | streaming position | ring blocks
@@ -315,80 +273,55 @@ pu_dstream* pu_dstream_open(const pu_stream_params* params, int count, int devic
             h.ring_off = bytes;
             bytes += round16((size_t)h.p.num_cores * (16 * 8 + 4));
         }
-    s->bytes = bytes;
 
-    if (hipSetDevice(device) != hipSuccess) return fail(PU_ENODEV, "hipSetDevice failed");
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return fail(PU_EIO, "stream create failed");
-    if (hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) return fail(PU_EIO, "event create failed");
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(PU_ENOMEM, "pu_dstream_open: " + std::to_string(bytes) + " bytes of device memory for the state of " +
-                                   std::to_string(count) + " streams (" + std::to_string(cores) +
-                                   " cores) could not be allocated");
-    }
-    s->base = (uint8_t*)p;
+    if (s->open(device, bytes, "pu_dstream_open: the state of " + std::to_string(count) + " streams (" +
+                                   std::to_string(cores) + " cores)") != 0)
+        return pu::drop_set(s);
     s->hdrs = (DsHdr*)s->base;
     s->rng = (uint64_t*)(s->base + off_rng);
     s->cyc = (int64_t*)(s->base + off_cyc);
     s->spos = (uint64_t*)(s->base + off_pos);
     if (hipMemcpyAsync(s->hdrs, hdrs.data(), (size_t)count * sizeof(DsHdr), hipMemcpyHostToDevice, s->stream) != hipSuccess)
-        return fail(PU_EIO, "header upload failed");
+        return pu::drop_set(s, PU_EIO, "header upload failed");
     hipLaunchKernelGGL(dstream_init_kernel, dim3((unsigned)count), dim3(kThreads), 0, s->stream, s->hdrs, s->base, s->rng,
                        s->cyc, s->spos);
-    if (hipGetLastError() != hipSuccess) return fail(PU_EIO, "state initialisation launch failed");
-    if (hipEventRecord(s->ev, s->stream) != hipSuccess) return fail(PU_EIO, "event record failed");
-    s->ev_recorded = true;
-    s->last = s->stream;
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return fail(PU_EIO, "state initialisation failed");   // hdrs is a local
+    if (s->record_after(s->stream, "pu_dstream_open") != 0) return pu::drop_set(s);
+    if (hipStreamSynchronize(s->stream) != hipSuccess)   // hdrs is a local
+        return pu::drop_set(s, PU_EIO, "state initialisation failed");
     return s;
 }
 
-void pu_dstream_close(pu_dstream* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    (void)wait_outstanding(s);
-    release(s);
-}
+void pu_dstream_close(pu_dstream* s) { pu::close_set(s); }
 
 int pu_dstream_next(pu_dstream* s, void* d_out, size_t n_each, size_t stride, int fmt, uint64_t* d_got,
                     void* hip_stream) {
-    if (!s || (fmt != PU_REQ_FMT_32 && fmt != PU_REQ_FMT_16) || stride < n_each || (!d_out && n_each) ||
-        ((uintptr_t)d_out & 15))
+    if (!s || !pu::req_fmt_ok(fmt) || stride < n_each || (!d_out && n_each) || ((uintptr_t)d_out & 15))
         return pu::set_error(PU_EINVAL, "pu_dstream_next: bad arguments");
     if (fmt == PU_REQ_FMT_16 && !s->refuse16.empty()) return pu::set_error(PU_ERANGE, s->refuse16);
-    if (hipSetDevice(s->device) != hipSuccess) return pu::set_error(PU_ENODEV, "hipSetDevice failed");
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : s->stream;
-    // the state is the set's: a call on another stream runs after the call before it
-    if (st != s->last && s->ev_recorded && hipStreamWaitEvent(st, s->ev, 0) != hipSuccess)
-        return pu::set_error(PU_EIO, "ordering the call after the set's last call failed");
+    int rc = s->use();
+    if (rc) return rc;
+    hipStream_t st = s->pick(hip_stream);
+    rc = s->order_before(st);
+    if (rc) return rc;
     if (fmt == PU_REQ_FMT_16)
         hipLaunchKernelGGL(dstream_next_kernel<PU_REQ_FMT_16>, dim3((unsigned)s->count), dim3(kThreads), 0, st, s->hdrs,
                            s->base, s->rng, s->cyc, s->spos, d_out, (uint64_t)n_each, (uint64_t)stride, d_got);
     else
         hipLaunchKernelGGL(dstream_next_kernel<PU_REQ_FMT_32>, dim3((unsigned)s->count), dim3(kThreads), 0, st, s->hdrs,
                            s->base, s->rng, s->cyc, s->spos, d_out, (uint64_t)n_each, (uint64_t)stride, d_got);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pu::set_error(PU_EIO, std::string("pu_dstream_next: launch failed: ") + hipGetErrorString(e));
-    if (hipEventRecord(s->ev, st) != hipSuccess) return pu::set_error(PU_EIO, "event record failed");
-    s->ev_recorded = true;
-    s->last = st;
-    return 0;
+    return s->record_after(st, "pu_dstream_next");
 }
 
 int pu_dstream_positions(pu_dstream* s, int64_t* out, size_t n) {
     if (!s || (!out && n)) return pu::set_error(PU_EINVAL, "bad arguments");
     if (n > (size_t)s->count) return pu::set_error(PU_ERANGE, "more streams than the set holds");
     if (n == 0) return 0;
-    if (hipSetDevice(s->device) != hipSuccess) return pu::set_error(PU_ENODEV, "hipSetDevice failed");
-    int rc = wait_outstanding(s);
-    if (rc) return rc;
-    // on the set's own (non-blocking) stream: a copy on the null stream would wait for every blocking stream
-    if (hipMemcpy2DAsync(out, sizeof(int64_t), (const uint8_t*)s->hdrs + offsetof(DsHdr, n), sizeof(DsHdr),
-                         sizeof(int64_t), n, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-        hipStreamSynchronize(s->stream) != hipSuccess)
-        return pu::set_error(PU_EIO, "reading the stream positions failed");
-    return 0;
+    return s->read_back(
+        [&](hipStream_t st) {
+            return hipMemcpy2DAsync(out, sizeof(int64_t), (const uint8_t*)s->hdrs + offsetof(DsHdr, n), sizeof(DsHdr),
+                                    sizeof(int64_t), n, hipMemcpyDeviceToHost, st) == hipSuccess;
+        },
+        "reading the stream positions failed");
 }
 
 uint64_t pu_dstream_state_bytes(const pu_dstream* s) { return s ? (uint64_t)s->bytes : 0; }

@@ -9,13 +9,7 @@
 #include <cstdint>
 
 #include "../../include/primeuncore.h"
-
-#if defined(__HIP__) || defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define PU_HD __host__ __device__
-#else
-#define PU_HD
-#endif
+#include "pu_hd.h"
 
 namespace pu_stream_step {
 

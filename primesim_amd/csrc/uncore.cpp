@@ -56,6 +56,12 @@ int set_error(int code, const std::string& msg) {
     return code;
 }
 
+int device_check(int device, const char* note) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && device >= 0 && device < ndev) return 0;
+    return set_error(PU_ENODEV, std::string("no HIP device available") + (note ? " (" + std::string(note) + ")" : ""));
+}
+
 }  // namespace pu
 
 namespace {
@@ -809,11 +815,7 @@ pu_handle* pu_create(const pu_sim_cfg* cfg, int num_replicas, int device) {
     Geo geo;
     if (build_geo(cfg, &geo) != 0) return nullptr;
     pu::jit_note_gpu();   // this process starts no compiler from here on
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        pu::set_error(PU_ENODEV, "no HIP device available (the engine has no CPU fallback)");
-        return nullptr;
-    }
+    if (pu::device_check(device, "the engine has no CPU fallback") != 0) return nullptr;
     pu_handle* h = new pu_handle();
     h->cfg = *cfg;
     h->geo = geo;
@@ -1119,7 +1121,7 @@ int pu_run_device(pu_handle* h, const pu_req* d_reqs, const uint64_t* d_off, int
 }
 
 int pu_set_device_req_format(pu_handle* h, int fmt) {
-    if (!h || (fmt != PU_REQ_FMT_32 && fmt != PU_REQ_FMT_16)) return pu::set_error(PU_EINVAL, "bad arguments");
+    if (!h || !pu::req_fmt_ok(fmt)) return pu::set_error(PU_EINVAL, "bad arguments");
     std::lock_guard<std::mutex> lk(h->mu);
     h->dev_req_flags = fmt == PU_REQ_FMT_16 ? PU_KF_REQ16 : 0u;
     return 0;
@@ -1129,12 +1131,12 @@ int pu_pack_req16(const pu_req* in, size_t n, pu_req16* out) {
     if (n && (!in || !out)) return pu::set_error(PU_EINVAL, "bad arguments");
     for (size_t i = 0; i < n; i++) {
         const pu_req& q = in[i];
-        if (q.timer < 0 || q.timer >= (int64_t)1 << 40 || q.core < 0 || q.core >= 1 << 16 || q.prog_id < 0 ||
-            q.prog_id >= 64 || q.mem_type > 1 || q.batch_start > 1 || q.tag != 0)
+        if (q.timer < 0 || q.timer >= (int64_t)1 << PU_REQ16_TIMER_BITS || q.core < 0 ||
+            q.core >= 1 << PU_REQ16_CORE_BITS || q.prog_id < 0 || q.prog_id >= 1 << PU_REQ16_PROG_BITS ||
+            q.mem_type > 1 || q.batch_start > 1 || q.tag != 0)
             return pu::set_error(PU_ERANGE, "request " + std::to_string(i) + " does not fit pu_req16");
         out[i].a = q.addr;
-        out[i].b = (uint64_t)q.timer | (uint64_t)(uint32_t)q.core << 40 | (uint64_t)(uint32_t)q.prog_id << 56 |
-                   (uint64_t)q.mem_type << 62 | (uint64_t)q.batch_start << 63;
+        out[i].b = PU_REQ16_B(q.timer, q.core, q.prog_id, q.mem_type, q.batch_start);
     }
     return 0;
 }
@@ -1494,9 +1496,8 @@ struct DevBufs {
 
 int unit_prepare(int device) {
     pu::jit_note_gpu();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
-        return pu::set_error(PU_ENODEV, "no HIP device available");
+    int rc = pu::device_check(device);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(device), PU_ENODEV);
     return 0;
 }

@@ -168,6 +168,35 @@ def last_error() -> str:
     return lib().pu_last_error().decode()
 
 
+class _Owner:
+    """Owns one native handle, `_h` (set once the library has created it):
+    `_handle()` gives it or raises `_no_handle`, `close()` hands it to the
+    library's entry `_close` and is run again, harmlessly, on collection."""
+    _h: Optional[int] = None
+    _close = ""
+    _no_handle = ""
+
+    def _handle(self) -> int:
+        if not self._h:
+            raise UncoreError(self._no_handle)
+        return self._h
+
+    def close(self) -> None:
+        if self._h:
+            getattr(lib(), self._close)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _state_bytes(entry: str, doc: str) -> property:
+    return property(lambda self: int(getattr(lib(), entry)(self._handle())), doc=doc)
+
+
 # PU_E* codes (include/primeuncore.h).  pu_access returns them in-band (a
 # wrapped delay may collide with one); the mirror uses pu_access_status.
 PU_ERRORS = (-5, -12, -19, -22, -34, -71, -95)
@@ -308,15 +337,15 @@ def stream_fits_req16(spec: StreamSpec) -> bool:
     return rc == 0
 
 
-class DeviceStreamSet:
+class DeviceStreamSet(_Owner):
     """StreamSet on the device (pu_dstream_*): the generator state of every
     stream lives in device memory and `next_into` writes each stream's next
     chunk into device memory, ready for run_device / run_device_sliced /
     run_device_pool, byte for byte what StreamSet produces.  Pointers are plain
     integers (tensor.data_ptr()).  Needs a GPU: there is no host fallback."""
+    _close, _no_handle = "pu_dstream_close", "DeviceStreamSet is closed"
 
     def __init__(self, specs: list[StreamSpec], device: int = 0):
-        self._h = None
         self._n = len(specs)
         arr = (A.StreamParams * max(1, len(specs)))(*[sp.params() for sp in specs])
         h = lib().pu_dstream_open(arr, len(specs), device)
@@ -324,18 +353,10 @@ class DeviceStreamSet:
             raise UncoreError(f"pu_dstream_open: {last_error()}")
         self._h = h
 
-    def _handle(self) -> int:
-        if not self._h:
-            raise UncoreError("DeviceStreamSet is closed")
-        return self._h
-
     def __len__(self) -> int:
         return self._n
 
-    @property
-    def state_bytes(self) -> int:
-        """Device memory the set's generator state takes."""
-        return int(lib().pu_dstream_state_bytes(self._handle()))
+    state_bytes = _state_bytes("pu_dstream_state_bytes", "Device memory the set's generator state takes.")
 
     def next_into(self, d_out_ptr: int, n_each: int, stride: Optional[int] = None, fmt: int = A.PU_REQ_FMT_32,
                   d_got_ptr: int = 0, stream_ptr: int = 0) -> None:
@@ -355,17 +376,6 @@ class DeviceStreamSet:
         if lib().pu_dstream_positions(self._handle(), out.ctypes.data, self._n) != 0:
             raise UncoreError(f"pu_dstream_positions: {last_error()}")
         return out
-
-    def close(self) -> None:
-        if self._h:
-            lib().pu_dstream_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------- delay summaries
@@ -401,15 +411,15 @@ def summarize_delays(reqs: np.ndarray, delays: np.ndarray, num_cores: Optional[i
     return out[0], cnt, sm
 
 
-class DeviceDelaySummary:
+class DeviceDelaySummary(_Owner):
     """Per-replica delay summaries kept on the device (pu_dsum_*): `add` folds every
     replica's records [begin[r], end[r]) of device request and delay arrays into its
     running summary, bit for bit what summarize_delays gives.  num_cores (one entry per
     replica) adds per-core (count, sum) tables.  Pointers are plain integers
     (tensor.data_ptr()).  Needs a GPU: there is no host fallback."""
+    _close, _no_handle = "pu_dsum_close", "DeviceDelaySummary is closed"
 
     def __init__(self, count: int, num_cores=None, device: int = 0):
-        self._h = None
         self._n = count
         self._nc = None
         arr = None
@@ -423,18 +433,10 @@ class DeviceDelaySummary:
             raise UncoreError(f"pu_dsum_open: {last_error()}")
         self._h = h
 
-    def _handle(self) -> int:
-        if not self._h:
-            raise UncoreError("DeviceDelaySummary is closed")
-        return self._h
-
     def __len__(self) -> int:
         return self._n
 
-    @property
-    def state_bytes(self) -> int:
-        """Device memory the set holds."""
-        return int(lib().pu_dsum_state_bytes(self._handle()))
+    state_bytes = _state_bytes("pu_dsum_state_bytes", "Device memory the set holds.")
 
     def add(self, d_reqs_ptr: int, d_delay_ptr: int, d_begin_ptr: int, d_end_ptr: int, fmt: int = A.PU_REQ_FMT_32,
             stream_ptr: int = 0) -> None:
@@ -468,17 +470,6 @@ class DeviceDelaySummary:
         rc = lib().pu_dsum_reset(self._handle())
         if rc != 0:
             raise UncoreError(f"pu_dsum_reset: {last_error()} ({rc})")
-
-    def close(self) -> None:
-        if self._h:
-            lib().pu_dsum_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------- MsgMem logs
@@ -567,11 +558,11 @@ class InsMem:
     rec_thread_id: int = 0
 
 
-class UncoreManager:
+class UncoreManager(_Owner):
     """reference UncoreManager (uncore_manager.h:51-68) backed by the HIP engine."""
+    _close, _no_handle = "pu_destroy", "UncoreManager not initialised"
 
     def __init__(self) -> None:
-        self._h: Optional[int] = None
         self.cfg: Optional[A.SimCfg] = None
         self.replicas = 0
 
@@ -583,22 +574,6 @@ class UncoreManager:
         self._h = h
         self.cfg = cfg
         self.replicas = replicas
-
-    def close(self) -> None:
-        if self._h:
-            lib().pu_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self) -> int:
-        if not self._h:
-            raise UncoreError("UncoreManager not initialised")
-        return self._h
 
     def reset(self) -> None:
         if lib().pu_reset(self._handle()) != 0:

@@ -8,10 +8,9 @@ import re
 import pytest
 
 import primesim_amd as P
+from abi_helpers import ROOT, gpu_present
 from primesim_amd import config as CF
 from primesim_amd.uncore import lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def declared_symbols():
@@ -46,15 +45,7 @@ def test_version_and_error_strings():
     assert isinstance(P.uncore.last_error(), str)
 
 
-def _gpu_present() -> bool:
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
-
-
-@pytest.mark.skipif(_gpu_present(), reason="checks the no-GPU path")
+@pytest.mark.skipif(gpu_present(), reason="checks the no-GPU path")
 def test_no_gpu_fails_loudly():
     um = P.UncoreManager()
     with pytest.raises(P.UncoreError, match="no HIP device"):
@@ -85,7 +76,7 @@ def test_config_validation_before_device(mutate, msg):
     assert msg in P.uncore.last_error()
 
 
-@pytest.mark.skipif(_gpu_present(), reason="checks the no-GPU path")
+@pytest.mark.skipif(gpu_present(), reason="checks the no-GPU path")
 @pytest.mark.parametrize("mutate", [lambda s: s["system"].update(tlb_enable=1),
                                     lambda s: s["system"].update(sys_type=1),
                                     lambda s: s["system"].update(sys_type=1, tlb_enable=1),

@@ -8,27 +8,17 @@ stand-alone program built with the host's address and undefined-behaviour
 sanitizers)."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import pytest
 
 import primesim_amd as P
+from abi_helpers import ROOT, gpu_present, run_cpp_check
 from primesim_amd import _abi as A
 from primesim_amd import uncore as U
 from primesim_amd.uncore import lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = [A.PU_STREAM_PRIVATE_STREAMING, A.PU_STREAM_SHARED_UNIFORM, A.PU_STREAM_MULTIPROGRAM,
          A.PU_STREAM_UNIFORM_HOTSPOT, A.PU_STREAM_PRODUCER_CONSUMER, A.PU_STREAM_UNIFORM]
-
-
-def _gpu_present() -> bool:
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def _params(specs):
@@ -61,7 +51,7 @@ def test_open_validates_every_entry_before_a_device(bad, where):
         P.DeviceStreamSet(specs)
 
 
-@pytest.mark.skipif(_gpu_present(), reason="checks the no-GPU path")
+@pytest.mark.skipif(gpu_present(), reason="checks the no-GPU path")
 def test_open_without_a_gpu_fails_loudly():
     assert not lib().pu_dstream_open(_params([GOOD, GOOD]), 2, 0)
     assert "no HIP device" in U.last_error()
@@ -144,15 +134,4 @@ def test_mirror_declares_every_dstream_entry():
 
 
 def test_scan_and_cut_rule_equals_the_sequential_loop(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = tmp_path / "stream_cut_check"
-    # the sanitizer runtimes linked into the program itself: it then runs whatever else the loader brings in
-    static = ["-static-libsan"] if "clang" in os.path.basename(cxx) else ["-static-libasan", "-static-libubsan"]
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=all", *static, "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "stream_cut_check.cpp")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.startswith("OK 3000 rounds")
+    assert run_cpp_check(tmp_path, "stream_cut_check.cpp").startswith("OK 3000 rounds")

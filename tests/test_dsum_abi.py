@@ -6,26 +6,15 @@ with a loop of comparisons (tests/cpp/delay_bucket_check.cpp, a stand-alone prog
 built with the host's address and undefined-behaviour sanitizers)."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import primesim_amd as P
+from abi_helpers import ROOT, gpu_present, run_cpp_check
 from primesim_amd import _abi as A
 from primesim_amd import uncore as U
 from primesim_amd.uncore import lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _gpu_present() -> bool:
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def _i32(*v):
@@ -60,7 +49,7 @@ def test_python_open_wants_one_num_cores_per_replica():
         P.DeviceDelaySummary(3, num_cores=[4, 4])
 
 
-@pytest.mark.skipif(_gpu_present(), reason="checks the no-GPU path")
+@pytest.mark.skipif(gpu_present(), reason="checks the no-GPU path")
 def test_open_without_a_gpu_fails_loudly():
     assert not lib().pu_dsum_open(2, None, 0)
     assert "no HIP device" in U.last_error()
@@ -149,15 +138,4 @@ def test_mirror_declares_every_dsum_entry():
 
 
 def test_bucket_rule_equals_a_loop_of_comparisons(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = tmp_path / "delay_bucket_check"
-    # the sanitizer runtimes linked into the program itself: it then runs whatever else the loader brings in
-    static = ["-static-libsan"] if "clang" in os.path.basename(cxx) else ["-static-libasan", "-static-libubsan"]
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=all", *static, "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "delay_bucket_check.cpp")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.startswith("OK 1000068 delays")
+    assert run_cpp_check(tmp_path, "delay_bucket_check.cpp").startswith("OK 1000068 delays")

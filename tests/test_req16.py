@@ -3,16 +3,20 @@ bench's timed window uses:
 
 * CPU: pu_pack_req16 keeps every field the engine reads (decoded here with
   the layout the header states) and refuses a record that does not fit, at
-  each field's boundary;
+  each field's boundary; the header's PU_REQ16_* macros are that layout
+  (tests/cpp/req16_layout_check.cpp, a stand-alone program);
 * GPU: the device-run entry points under PU_REQ_FMT_16 give the delays,
   counters and completion cycles of the same requests as 32-B pu_req, and
   those of the CPU restatement (pool, time-sliced and unsliced launches, open
   and closed loop, C2 and the bench's C4 kernel).
 """
+import os
+
 import numpy as np
 import pytest
 
 import primesim_amd as P
+from abi_helpers import ROOT, run_cpp_check
 from primesim_amd import _abi as A
 from primesim_amd import config as CF
 from primesim_amd import uncore as U
@@ -62,6 +66,13 @@ def test_pack_req16_refuses_what_does_not_fit(field, value):
 
 def test_pack_req16_empty():
     assert U.pack_req16(np.zeros(0, dtype=A.REQ_DTYPE)).shape == (0, 2)
+
+
+def test_req16_macros_are_the_layout(tmp_path):
+    """PU_REQ16_B and the extract macros of the header against the layout in literal shifts
+    (tests/cpp/req16_layout_check.cpp): 4 x 4 x 4 x 2 x 2 edge combinations and 100,000 random records."""
+    out = run_cpp_check(tmp_path, "req16_layout_check.cpp", includes=(os.path.join(ROOT, "include"),))
+    assert out.startswith("OK 100256 records")
 
 
 # ---------------------------------------------------------------- GPU parity
