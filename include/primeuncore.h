@@ -651,6 +651,103 @@ void     pu_dsum_host_init(pu_dsum_replica* acc);
 int      pu_dsum_host_add(pu_dsum_replica* acc, uint64_t* core_count, int64_t* core_sum, int num_cores,
                           const void* reqs, int fmt, const int32_t* delays, size_t n);
 
+/* End-of-run results gathered on the device (no reference counterpart; the fourth stage of
+ * a device-side ensemble: pu_dstream_next -> pu_run_device / _sliced / _pool ->
+ * pu_dsum_add -> pu_dres_gather).  One kernel launch reads, for every replica of a range,
+ * what pu_stats_get and pu_core_completion would copy one replica at a time, plus the
+ * engine's exact visit counts per link and bus, into one dense record per replica; one
+ * copy brings the records to the host.  A gather is a snapshot, not an accumulator:
+ * gathering twice without a run in between gives the same bytes.  Every figure is an
+ * integer, so the device record equals pu_dres_host_gather's byte for byte.
+ *
+ * The rules (primesim_amd/csrc/run_results_step.h):
+ *   queues      [0, nlinks) are the links, [nlinks, nqueues) the buses, in the engine's
+ *               record numbering (pu_config_queue_ends).  For a link, n counts all visits
+ *               and n1 the visits of block-length packets: the flits sent over it are
+ *               header_flits * n + (plen_blk - header_flits) * n1, where plen_blk =
+ *               header_flits + ceil(last-level block size / data_width).  A bus carries one
+ *               packet length (bus_latency), so its n1 is reported as 0.
+ *   busiest     link_max_* / bus_max_*: the largest n of the range and, among equal
+ *               counts, the lowest queue id (a bus's id counts from nlinks as in the map).
+ *               A configuration without links (buses) reports id -1 and 0 visits; one with
+ *               links none of which was visited reports 0 visits at id 0 (nlinks for buses).
+ *               links_used / buses_used count the queues with n > 0.
+ *   completion  over the cores that have completed a request, i.e. whose cycle is not the
+ *               -1 that a reset writes and pu_core_completion returns for an idle core:
+ *               cores_done of them, completion_max (the simulated end cycle), _min and
+ *               _sum; with none: INT64_MIN, INT64_MAX and 0.
+ *   stats       field for field what pu_stats_get returns.
+ *
+ * pu_dres_open: a set for all replicas of h, on h's device.  flags: 0, or PU_DRES_QUEUES
+ * to keep the per-queue map (n and n1 of every queue of every replica: 16 B per queue and
+ * replica on top of the 448-B records, e.g. 31,744 B per replica of a 32x32 mesh, which is
+ * why it is optional).  The set must be closed before h is destroyed.
+ *
+ * pu_dres_gather: replicas [first, first + n), asynchronous on hip_stream (NULL = the
+ * set's own stream).  Ordering: the caller orders a gather after the run it wants to see --
+ * the same stream, or pu_synchronize first; a gather orders itself after the set's earlier
+ * calls whatever stream they were on.  It first joins a resident kernel of h (whose queue
+ * headers live on chip until it leaves).  The other replicas' records and map rows stay as
+ * they were.
+ *
+ * pu_dres_read: records of replicas [first, first + n).  pu_dres_read_queues: n and n1 of
+ * every queue of one replica as of its last gather (either output may be NULL; cap >=
+ * nqueues entries each); PU_ENOTSUP for a set opened without PU_DRES_QUEUES.
+ * pu_dres_read_queue_totals: per queue, the sums of n and n1 over the replicas of the last
+ * gather that was launched (all zero before the first, and after a gather of no replica),
+ * by two more launches without atomics on the set's own stream, after that gather.  A set
+ * with the map sums the map: a snapshot, like the records.  A set without it sums the queue
+ * headers as they are at this call: after another run the two kinds of set answer
+ * differently for the same gather, so read the totals before the next run, or keep the
+ * map.  pu_dres_read*, and pu_dres_close, wait only for the work
+ * of this set (the event of its last call), never for the device.
+ *
+ * pu_dres_host_gather: the same record, and optionally the same n / n1 rows, for one
+ * replica by plain copies (pu_stats_get, pu_core_completion, and copies of the run state and
+ * the queue headers).  pu_num_links / pu_num_queues: links / queues (links, then buses) per
+ * replica of a handle; pu_dres_nqueues: the queues of a set's replicas (0 for NULL).  pu_dres_state_bytes: device memory the set holds.
+ *
+ * pu_config_queue_ends: which edge or bus queue q of cfg is; host only, needs no device.
+ * kind 0 / 1 / 2: a link along x / y / z between the network nodes a < b; 3: a bus, a =
+ * its cache level, b = the cache's index in that level; -1 (a = b = -1): q names no queue.
+ * Node (x, y, z) of a mesh of width w has id z*w*w + y*w + x.  2-D: record y*(w-1) + x_low
+ * is the x link between (x_low, y) and (x_low + 1, y); record w*(w-1) + x*(w-1) + y_low
+ * the y link between (x, y_low) and (x, y_low + 1).  3-D: three blocks of w*w*(w-1)
+ * records: x at (z*w + y)*(w-1) + x_low, y at (z*w + x)*(w-1) + y_low, z at
+ * (y*w + x)*(w-1) + z_low.  The records cover the whole w x w (x w) grid even where the
+ * configuration has fewer nodes.
+ *
+ * Arguments are checked before any device call: a NULL handle or set, unknown flags:
+ * PU_EINVAL; first < 0, n < 0: PU_EINVAL; first + n > replicas, a replica out of range,
+ * cap too small: PU_ERANGE.  Returns 0 or PU_E*. */
+#define PU_DRES_QUEUES 1            /* keep the per-queue map [R][nqueues] */
+typedef struct pu_dres_replica {
+    pu_stats stats;                 /* field for field what pu_stats_get returns */
+    uint64_t processed;             /* RunState.processed */
+    int32_t  halted, cores_done;    /* RunState.halted; cores that have completed a request */
+    int64_t  completion_max, completion_min, completion_sum;
+    uint64_t link_visits, link_block_visits;   /* sum of n and of n1 over the links */
+    uint64_t link_max_visits;
+    int32_t  link_max_id, links_used;
+    uint64_t bus_visits, bus_max_visits;
+    int32_t  bus_max_id, buses_used;
+} pu_dres_replica;                  /* 448 bytes */
+
+typedef struct pu_dres pu_dres;
+pu_dres* pu_dres_open(pu_handle* h, int flags);
+void     pu_dres_close(pu_dres* s);
+int      pu_dres_gather(pu_dres* s, int first, int n, void* hip_stream);
+int      pu_dres_read(pu_dres* s, int first, int n, pu_dres_replica* out);
+int      pu_dres_read_queues(pu_dres* s, int replica, uint64_t* n_out, uint64_t* n1_out, size_t cap);
+int      pu_dres_read_queue_totals(pu_dres* s, uint64_t* n_out, uint64_t* n1_out, size_t cap);
+int      pu_dres_nqueues(const pu_dres* s);
+uint64_t pu_dres_state_bytes(const pu_dres* s);
+int      pu_num_links(const pu_handle* h);
+int      pu_num_queues(const pu_handle* h);
+int      pu_dres_host_gather(pu_handle* h, int replica, pu_dres_replica* out,
+                             uint64_t* n_out, uint64_t* n1_out, size_t cap);
+int      pu_config_queue_ends(const pu_sim_cfg* cfg, int q, int* kind, int* a, int* b);
+
 /* Trace files ("PUTRACE1": header, thread table, pu_req records). */
 int pu_trace_write(const char* path, const pu_req* reqs, size_t n,
                    const int32_t* thread_prog, const int32_t* thread_id, int num_threads);

@@ -129,6 +129,17 @@ class DsumReplica(C.Structure):         # pu_dsum_replica
     _fields_ = [("cls", DsumClass * 2), ("core_out_of_range", C.c_uint64)]
 
 
+class DresReplica(C.Structure):         # pu_dres_replica
+    _fields_ = [
+        ("stats", Stats), ("processed", C.c_uint64), ("halted", C.c_int32), ("cores_done", C.c_int32),
+        ("completion_max", C.c_int64), ("completion_min", C.c_int64), ("completion_sum", C.c_int64),
+        ("link_visits", C.c_uint64), ("link_block_visits", C.c_uint64), ("link_max_visits", C.c_uint64),
+        ("link_max_id", C.c_int32), ("links_used", C.c_int32),
+        ("bus_visits", C.c_uint64), ("bus_max_visits", C.c_uint64),
+        ("bus_max_id", C.c_int32), ("buses_used", C.c_int32),
+    ]
+
+
 class ServerOpts(C.Structure):          # pu_server_opts
     _fields_ = [
         ("socket_path", C.c_char_p), ("report_prefix", C.c_char_p), ("num_sessions", C.c_int32),
@@ -159,6 +170,25 @@ DSUM_CLASS_DTYPE = np.dtype([("count", "<u8"), ("sum", "<i8"), ("min", "<i4"), (
                              ("hist", "<u8", (PU_DSUM_BUCKETS,))])
 DSUM_DTYPE = np.dtype([("cls", DSUM_CLASS_DTYPE, (2,)), ("core_out_of_range", "<u8")])
 assert DSUM_DTYPE.itemsize == C.sizeof(DsumReplica) == 568
+# pu_level_stats / pu_stats / pu_dres_replica as numpy structured dtypes
+LEVEL_STATS_DTYPE = np.dtype([("ins", "<u8"), ("miss", "<u8"), ("evict", "<u8"), ("wb", "<u8")])
+STATS_DTYPE = np.dtype(
+    [(f, "<u8") for f in ("net_accesses", "net_distance", "net_total_delay", "net_router_delay", "net_link_delay",
+                          "net_inject_delay", "dram_accesses", "total_bus_contention")] +
+    [("total_num_broadcast", "<i8"), ("num_levels", "<i4"), ("_pad", "<i4"),
+     ("level", LEVEL_STATS_DTYPE, (PU_MAX_LEVELS,)), ("directory", LEVEL_STATS_DTYPE), ("tlb", LEVEL_STATS_DTYPE)] +
+    [(f, "<u8") for f in ("link_flits", "mg1_calls", "lockdown_calls", "bus_accesses", "requests", "error_flags",
+                          "dram_row_hits", "dram_row_empty", "dram_row_conflicts", "dram_bank_wait")])
+DRES_DTYPE = np.dtype([
+    ("stats", STATS_DTYPE), ("processed", "<u8"), ("halted", "<i4"), ("cores_done", "<i4"),
+    ("completion_max", "<i8"), ("completion_min", "<i8"), ("completion_sum", "<i8"),
+    ("link_visits", "<u8"), ("link_block_visits", "<u8"), ("link_max_visits", "<u8"),
+    ("link_max_id", "<i4"), ("links_used", "<i4"),
+    ("bus_visits", "<u8"), ("bus_max_visits", "<u8"), ("bus_max_id", "<i4"), ("buses_used", "<i4"),
+])
+assert STATS_DTYPE.itemsize == C.sizeof(Stats) == 352
+assert DRES_DTYPE.itemsize == C.sizeof(DresReplica) == 448
+PU_DRES_QUEUES = 1                       # pu_dres_open: keep the per-queue map
 assert C.sizeof(SimCfg) == 24 + C.sizeof(SysCfg)
 
 

@@ -2,11 +2,14 @@
 #pragma once
 
 #include <map>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "../../include/primeuncore.h"
+
+struct Geo;   // geometry.h
 
 namespace pu {
 
@@ -28,6 +31,22 @@ int run_device_flags(pu_handle* h, const pu_req* d_reqs, const uint64_t* d_off, 
 // that launch's request array of the first request that raised a
 // PU_ERRF_LIMITS bit (UINT64_MAX: none).
 int limit_positions(pu_handle* h, uint64_t* out, size_t n);
+
+// What another translation unit may see of a handle (pu_handle is uncore.cpp's):
+// the arena of its R replicas, the geometry (on the host), its device, and the
+// mutex that guards its launches.
+struct HandleView {
+    char* arena;
+    const Geo* geo;
+    int R, device;
+    std::mutex* mu;
+};
+HandleView handle_view(pu_handle* h);
+// Joins the handle's resident kernel, if one runs: its queue headers are in
+// device memory afterwards.  The caller holds the handle's mutex.
+int handle_resident_stop(pu_handle* h);
+// The geometry pu_create would build for cfg (0 or PU_E* with the error text); no device.
+int config_geometry(const pu_sim_cfg* cfg, Geo* out);
 
 // ThreadSched (reference src/thread_sched.cpp:55-91) with its quirks: the
 // first free core is taken, a busy core is marked with its prog id, a core is

@@ -1156,6 +1156,13 @@ int pu::limit_positions(pu_handle* h, uint64_t* out, size_t n) {
     return 0;
 }
 
+// The handle as the other device-side stages see it (common.h; run_results.hip).
+pu::HandleView pu::handle_view(pu_handle* h) {
+    return pu::HandleView{h->arena, &h->geo, h->R, h->device, &h->mu};
+}
+int pu::handle_resident_stop(pu_handle* h) { return resident_stop(h); }
+int pu::config_geometry(const pu_sim_cfg* cfg, Geo* out) { return build_geo(cfg, out); }
+
 int pu::run_device_flags(pu_handle* h, const pu_req* d_reqs, const uint64_t* d_off, int32_t* d_delay,
                          uint32_t extra_flags, bool use_replay_mode) {
     if (!h || !d_reqs || !d_off || !d_delay) return pu::set_error(PU_EINVAL, "bad arguments");

@@ -131,6 +131,19 @@ def lib() -> C.CDLL:
         "pu_dsum_host_init": (None, [P(A.DsumReplica)]),
         "pu_dsum_host_add": (C.c_int, [P(A.DsumReplica), P(C.c_uint64), P(C.c_int64), C.c_int, C.c_void_p, C.c_int,
                                        P(C.c_int32), C.c_size_t]),
+        "pu_dres_open": (C.c_void_p, [C.c_void_p, C.c_int]),
+        "pu_dres_close": (None, [C.c_void_p]),
+        "pu_dres_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+        "pu_dres_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(A.DresReplica)]),
+        "pu_dres_read_queues": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64), P(C.c_uint64), C.c_size_t]),
+        "pu_dres_read_queue_totals": (C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64), C.c_size_t]),
+        "pu_dres_nqueues": (C.c_int, [C.c_void_p]),
+        "pu_dres_state_bytes": (C.c_uint64, [C.c_void_p]),
+        "pu_num_links": (C.c_int, [C.c_void_p]),
+        "pu_num_queues": (C.c_int, [C.c_void_p]),
+        "pu_dres_host_gather": (C.c_int, [C.c_void_p, C.c_int, P(A.DresReplica), P(C.c_uint64), P(C.c_uint64),
+                                          C.c_size_t]),
+        "pu_config_queue_ends": (C.c_int, [P(A.SimCfg), C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]),
         "pu_trace_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]),
         "pu_alloc_core_replica": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
         "pu_dealloc_core_replica": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -470,6 +483,107 @@ class DeviceDelaySummary(_Owner):
         rc = lib().pu_dsum_reset(self._handle())
         if rc != 0:
             raise UncoreError(f"pu_dsum_reset: {last_error()} ({rc})")
+
+
+QUEUE_KINDS = ("x", "y", "z", "bus")     # pu_config_queue_ends: kind 0 .. 3
+
+
+def queue_ends(cfg: A.SimCfg, q: int) -> tuple[int, int, int]:
+    """(kind, a, b) of queue q of a configuration (pu_config_queue_ends; no device):
+    kind 0 / 1 / 2 a link along x / y / z between nodes a < b, 3 the bus of cache b of
+    level a, -1 (with a = b = -1) where q names no queue."""
+    kind, a, b = C.c_int(), C.c_int(), C.c_int()
+    rc = lib().pu_config_queue_ends(C.byref(cfg), q, C.byref(kind), C.byref(a), C.byref(b))
+    if rc != 0:
+        raise UncoreError(f"pu_config_queue_ends: {last_error()} ({rc})")
+    return kind.value, a.value, b.value
+
+
+def host_run_results(um: "UncoreManager", replica: int = 0, queues: bool = False):
+    """One replica's end-of-run record by plain copies (pu_dres_host_gather), as an
+    A.DRES_DTYPE record; with queues also the n and n1 of every queue."""
+    out = np.zeros(1, dtype=A.DRES_DTYPE)
+    nq = int(lib().pu_num_queues(um._handle())) if queues else 0
+    n = np.zeros(nq, dtype=np.uint64) if queues else None
+    n1 = np.zeros(nq, dtype=np.uint64) if queues else None
+    rc = lib().pu_dres_host_gather(um._handle(), replica, _as(out, A.DresReplica),
+                                   None if n is None else _as(n, C.c_uint64),
+                                   None if n1 is None else _as(n1, C.c_uint64), nq)
+    if rc != 0:
+        raise UncoreError(f"pu_dres_host_gather: {last_error()} ({rc})")
+    return (out[0], n, n1) if queues else out[0]
+
+
+class DeviceRunResults(_Owner):
+    """The end-of-run results of an UncoreManager's replicas gathered on the device
+    (pu_dres_*): `gather` snapshots every replica of a range in one launch -- the
+    counters of stats(), the fold of completion(), the run state and the visit counts
+    of the links and buses -- and `read` brings the records (A.DRES_DTYPE) to the host
+    in one copy.  queues=True keeps the per-queue map (16 B per queue and replica).
+    Close it before the UncoreManager.  Needs a GPU: host_run_results is the host path."""
+    _close, _no_handle = "pu_dres_close", "DeviceRunResults is closed"
+
+    def __init__(self, um: "UncoreManager", queues: bool = False):
+        self._um = um                      # the set reads the manager's replicas: keep it alive
+        self._n = int(lib().pu_num_replicas(um._handle()))
+        h = lib().pu_dres_open(um._handle(), A.PU_DRES_QUEUES if queues else 0)
+        if not h:
+            raise UncoreError(f"pu_dres_open: {last_error()}")
+        self._h = h
+        self._nq = int(lib().pu_dres_nqueues(h))
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def num_queues(self) -> int:
+        """Queues per replica: the links first, then the buses."""
+        return self._nq
+
+    @property
+    def num_links(self) -> int:
+        return int(lib().pu_num_links(self._um._handle()))
+
+    state_bytes = _state_bytes("pu_dres_state_bytes", "Device memory the set holds.")
+
+    def gather(self, first: int = 0, n: Optional[int] = None, stream_ptr: int = 0) -> None:
+        """Asynchronous on stream_ptr (a hipStream_t as an integer; 0 is the set's own
+        stream).  The caller orders it after the run it wants to see: the run's stream,
+        or synchronize() first."""
+        n = self._n - first if n is None else n
+        self._um._handle()                 # the set reads the manager's replicas: it must still be open
+        rc = lib().pu_dres_gather(self._handle(), first, n, stream_ptr or None)
+        if rc != 0:
+            raise UncoreError(f"pu_dres_gather: {last_error()} ({rc})")
+
+    def read(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Records of replicas [first, first + n) as of their last gather (waits for the set's calls)."""
+        n = self._n - first if n is None else n
+        out = np.zeros(max(n, 0), dtype=A.DRES_DTYPE)
+        rc = lib().pu_dres_read(self._handle(), first, n, _as(out, A.DresReplica))
+        if rc != 0:
+            raise UncoreError(f"pu_dres_read: {last_error()} ({rc})")
+        return out
+
+    def queues(self, replica: int) -> tuple[np.ndarray, np.ndarray]:
+        """(n, n1) per queue of one replica; raises for a set opened without queues=True."""
+        n, n1 = np.zeros(self._nq, dtype=np.uint64), np.zeros(self._nq, dtype=np.uint64)
+        rc = lib().pu_dres_read_queues(self._handle(), replica, _as(n, C.c_uint64), _as(n1, C.c_uint64), self._nq)
+        if rc != 0:
+            raise UncoreError(f"pu_dres_read_queues: {last_error()} ({rc})")
+        return n, n1
+
+    def queue_totals(self) -> tuple[np.ndarray, np.ndarray]:
+        """(n, n1) per queue summed over the replicas of the last gather.  A set opened with
+        queues=True sums its map: a snapshot, like the records.  A set without it sums the queue
+        headers as they are at this call, so after another run the two kinds of set answer
+        differently for the same gather: read the totals before the next run, or keep the map."""
+        self._um._handle()                 # without the map the totals are read from the manager's replicas
+        n, n1 = np.zeros(self._nq, dtype=np.uint64), np.zeros(self._nq, dtype=np.uint64)
+        rc = lib().pu_dres_read_queue_totals(self._handle(), _as(n, C.c_uint64), _as(n1, C.c_uint64), self._nq)
+        if rc != 0:
+            raise UncoreError(f"pu_dres_read_queue_totals: {last_error()} ({rc})")
+        return n, n1
 
 
 # ---------------------------------------------------------------- MsgMem logs

@@ -10,6 +10,12 @@ class (a bucket b > 0 holds delays 2^(b-1) .. 2^b - 1; bucket 0 holds delays <= 
 cores out of range and the engine's error flags.  Needs a GPU: there is no CPU fallback.
 
   python tools/ensemble_summary.py --preset C1 --kind 1 --replicas 4 --chunk 2000 --chunks 2
+
+With --results the end-of-run results are gathered on the device too, once, after the
+last chunk (DeviceRunResults.gather on the same stream; 448 B per replica more): every
+replica's line gains a "results" object -- requests, the simulated end cycle, link
+visits, the busiest link with its two ends, network and DRAM counters -- and one last
+line lists the ensemble's ten busiest links, by visits summed over the replicas.
 """
 from __future__ import annotations
 
@@ -54,6 +60,38 @@ def replica_line(r: int, seed: int, s, flags: int) -> dict:
     return line
 
 
+def link_entry(cfg, q: int, visits: int, block_visits=None) -> dict:
+    """Queue q of the configuration with its ends (pu_config_queue_ends) and its visit count."""
+    import primesim_amd as P
+    from primesim_amd import uncore as U
+    kind, a, b = P.queue_ends(cfg, q)
+    e = {"id": q, "kind": U.QUEUE_KINDS[kind] if kind >= 0 else None, "a": a, "b": b, "visits": int(visits)}
+    if block_visits is not None:
+        e["block_visits"] = int(block_visits)
+    return e
+
+
+def results_object(cfg, rec) -> dict:
+    """One replica's end-of-run record (A.DRES_DTYPE) as the "results" object of its line."""
+    st, done = rec["stats"], int(rec["cores_done"])
+    return {"requests": int(st["requests"]), "processed": int(rec["processed"]), "halted": int(rec["halted"]),
+            "cores_done": done, "end_cycle": int(rec["completion_max"]) if done else None,
+            "link_visits": int(rec["link_visits"]), "link_block_visits": int(rec["link_block_visits"]),
+            "links_used": int(rec["links_used"]),
+            "hottest_link": link_entry(cfg, int(rec["link_max_id"]), rec["link_max_visits"])
+            if int(rec["link_max_id"]) >= 0 else None,
+            "bus_visits": int(rec["bus_visits"]),
+            "net_accesses": int(st["net_accesses"]), "net_distance": int(st["net_distance"]),
+            "net_total_delay": int(st["net_total_delay"]), "link_flits": int(st["link_flits"]),
+            "dram_accesses": int(st["dram_accesses"])}
+
+
+def hottest_links(cfg, n, n1, nlinks: int, top: int = 10) -> list:
+    """The `top` links with the most visits (lowest id first among equals), from per-queue totals."""
+    order = sorted(range(nlinks), key=lambda q: (-int(n[q]), q))[:top]
+    return [link_entry(cfg, q, n[q], n1[q]) for q in order]
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     g = ap.add_mutually_exclusive_group()
@@ -65,6 +103,7 @@ def main() -> int:
     ap.add_argument("--chunks", type=int, default=2)
     ap.add_argument("--seed-base", type=int, default=1, help="replica r streams with seed seed-base + r")
     ap.add_argument("--fmt", type=int, choices=(32, 16), default=32, help="device request records: pu_req or pu_req16")
+    ap.add_argument("--results", action="store_true", help="also gather the end-of-run results on the device")
     args = ap.parse_args()
 
     import torch
@@ -97,6 +136,9 @@ def main() -> int:
     um.init(cfg, replicas=R)
     dss = P.DeviceStreamSet(specs)
     dsum = P.DeviceDelaySummary(R, num_cores=[nc] * R)
+    dres = P.DeviceRunResults(um) if args.results else None
+    records = totals = None
+    nlinks = 0
     try:
         for prog, th in P.stream_threads(specs[0]):
             um.allocCore(prog, th)
@@ -105,18 +147,31 @@ def main() -> int:
             dss.next_into(d_reqs.data_ptr(), n, fmt=fmt, stream_ptr=sp)
             um.run_device(d_reqs.data_ptr(), d_off.data_ptr(), d_del.data_ptr(), sp)
             dsum.add(d_reqs.data_ptr(), d_del.data_ptr(), d_off.data_ptr(), d_off.data_ptr() + 8, fmt=fmt, stream_ptr=sp)
+        if dres is not None:
+            dres.gather(stream_ptr=sp)                                  # one launch, after the last chunk
         summaries = dsum.read()                                         # waits for the last add
+        if dres is not None:
+            records = dres.read()                                       # waits for the gather
+            totals = dres.queue_totals()
+            nlinks = dres.num_links
         stream.synchronize()
         if int(dss.positions().min()) != n * args.chunks:
             print("ensemble_summary: a stream ended before its last chunk", file=sys.stderr)
             return 1
         flags = um.error_flags(R)
     finally:
+        if dres is not None:
+            dres.close()
         dsum.close()
         dss.close()
         um.close()
     for r in range(R):
-        print(json.dumps(replica_line(r, args.seed_base + r, summaries[r], int(flags[r]))))
+        line = replica_line(r, args.seed_base + r, summaries[r], int(flags[r]))
+        if records is not None:
+            line["results"] = results_object(cfg, records[r])
+        print(json.dumps(line))
+    if records is not None:
+        print(json.dumps({"replicas": R, "hottest_links": hottest_links(cfg, totals[0], totals[1], nlinks)}))
     return 0
 
 
