@@ -748,6 +748,84 @@ int      pu_dres_host_gather(pu_handle* h, int replica, pu_dres_replica* out,
                              uint64_t* n_out, uint64_t* n1_out, size_t cap);
 int      pu_config_queue_ends(const pu_sim_cfg* cfg, int q, int* kind, int* a, int* b);
 
+/* Log-linear delay histograms kept on the device (no reference counterpart; a stage beside
+ * pu_dsum_add on the same stream: pu_dstream_next -> pu_run_device -> pu_dsum_add ->
+ * pu_dhist_add).  The 32 power-of-two buckets of pu_dsum_replica place a quantile within a
+ * factor of two; these place it within 3.2 %, and exactly below 64 cycles, still without a
+ * delay on the host.  Every figure is an exact integer and independent of the order of the
+ * records, so the device result equals the host fold (pu_dhist_host_add) bit for bit, and
+ * histograms add elementwise: chunks, replicas and ranks sum what they read.
+ *
+ * The rule (primesim_amd/csrc/delay_hist_step.h):
+ *   class     as for pu_dsum_*: 0 = read, 1 = write (pu_req: mem_type == PU_WR).
+ *   bucket    of a delay d (int32): 0 for d <= 0 (the meaning of pu_dsum's bucket 0); d itself
+ *             for 1 <= d < 64; otherwise, with o = 31 - clz(d) (6 .. 30),
+ *             64 + (o - 6) * 32 + ((d >> (o - 5)) - 32): every octave in 2^PU_DHIST_SUB_BITS
+ *             equal parts.  INT32_MAX is in bucket 863 = PU_DHIST_BUCKETS - 1.  Buckets 1 .. 863
+ *             tile [1, 2^31 - 1]; from bucket 64 on a bucket's width is <= its lower bound / 32.
+ *   bounds    bucket 0 is [INT32_MIN, 0]; bucket k < 64 is [k, k]; bucket k >= 64, with
+ *             j = k - 64, o = 6 + j / 32, m = 32 + j % 32: [m << (o - 5), ((m + 1) << (o - 5)) - 1].
+ *   coarse    every fine bucket lies inside one bucket of pu_dsum_class.hist: 0 -> 0, k < 64 ->
+ *             32 - clz(k), k >= 64 -> 7 + (k - 64) / 32.
+ *   layout    uint64_t hist[2][PU_DHIST_BUCKETS] per replica (13,824 B); a class's count is the
+ *             sum of its buckets.
+ *   quantile  nearest rank.  A quantile is given in parts per million, ppm in [0, 1,000,000];
+ *             rank = max(1, ceil(count * ppm / 10^6)), computed exactly through the 128-bit
+ *             product; the answer is the lowest bucket whose inclusive running count reaches
+ *             rank, or -1 for an empty class.  ppm 0 answers the minimum's bucket, 10^6 the
+ *             maximum's.
+ *
+ * pu_dhist_open: `count` replicas on `device`; 13,824 B of device memory per replica plus the
+ * quantile records and the slabs of the ensemble total.  NULL + pu_last_error() on failure
+ * ("no HIP device" where there is none: the set has no CPU fallback; PU_ENOMEM with the size
+ * asked for).
+ *
+ * pu_dhist_add: replica r counts the delays of records [d_begin[r], d_end[r]) into its
+ * histogram; the arguments, their checks (d_reqs 16-byte aligned) and the ordering are
+ * pu_dsum_add's, so one pair of index arrays serves both calls.
+ *
+ * pu_dhist_read: the histograms of replicas [first, first + n), 2 * PU_DHIST_BUCKETS
+ * counters each.  pu_dhist_quantiles: for replicas [first, first + n) and both classes, the
+ * class's count and the bucket of each of the nq (1 .. PU_DHIST_MAX_Q) quantiles ppm[0 .. nq),
+ * formed on the device: out holds 2 * n records, [replica][class]; bucket[q] is -1 for q >= nq.
+ * pu_dhist_read_total: the histogram summed over replicas [first, first + n) (2 *
+ * PU_DHIST_BUCKETS counters; all zero for n = 0), formed when read by two launches without
+ * atomics on the set's own stream.  pu_dhist_reset: every counter back to zero.
+ * pu_dhist_state_bytes: device memory the set holds.  Reading, resetting and closing wait
+ * only for the work of this set (the event of its last call), never for the device.
+ * A NULL set: PU_EINVAL, 0, no-op; first < 0, n < 0, nq outside 1 .. PU_DHIST_MAX_Q or a ppm
+ * above 10^6: PU_EINVAL; first + n > count: PU_ERANGE.
+ *
+ * Host twins, no device needed.  pu_dhist_host_add: n records added to hist
+ * (uint64_t [2][PU_DHIST_BUCKETS], zeroed by the caller).  pu_dhist_host_quantiles: one class's
+ * histogram (PU_DHIST_BUCKETS counters), its count to *count_out (may be NULL) and nq buckets
+ * to bucket_out.  pu_dhist_bucket_of: the bucket of a delay.  pu_dhist_bucket_bounds: the
+ * delays a bucket holds, both ends inclusive; PU_ERANGE for a bucket outside 0 .. 863. */
+#define PU_DHIST_SUB_BITS 5
+#define PU_DHIST_BUCKETS  864
+#define PU_DHIST_MAX_Q    8
+typedef struct pu_dhist_quantile {
+    uint64_t count;                     /* records of the class */
+    int32_t  bucket[PU_DHIST_MAX_Q];    /* per quantile asked for; -1: empty class, or not asked */
+} pu_dhist_quantile;                    /* 40 bytes */
+
+typedef struct pu_dhist pu_dhist;
+pu_dhist* pu_dhist_open(int count, int device);
+void      pu_dhist_close(pu_dhist* s);
+int       pu_dhist_add(pu_dhist* s, const void* d_reqs, int fmt, const int32_t* d_delay,
+                       const uint64_t* d_begin, const uint64_t* d_end, void* hip_stream);
+int       pu_dhist_read(pu_dhist* s, int first, int n, uint64_t* out);
+int       pu_dhist_quantiles(pu_dhist* s, int first, int n, const uint32_t* ppm, int nq,
+                             pu_dhist_quantile* out);
+int       pu_dhist_read_total(pu_dhist* s, int first, int n, uint64_t* out);
+int       pu_dhist_reset(pu_dhist* s);
+uint64_t  pu_dhist_state_bytes(const pu_dhist* s);
+int       pu_dhist_host_add(uint64_t* hist, const void* reqs, int fmt, const int32_t* delays, size_t n);
+int       pu_dhist_host_quantiles(const uint64_t* hist_one_class, const uint32_t* ppm, int nq,
+                                  uint64_t* count_out, int32_t* bucket_out);
+int       pu_dhist_bucket_of(int32_t d);
+int       pu_dhist_bucket_bounds(int bucket, int32_t* lo, int32_t* hi);
+
 /* Trace files ("PUTRACE1": header, thread table, pu_req records). */
 int pu_trace_write(const char* path, const pu_req* reqs, size_t n,
                    const int32_t* thread_prog, const int32_t* thread_id, int num_threads);

@@ -22,6 +22,7 @@ PU_STREAM_UNIFORM = 6
 PU_REQ_FMT_32, PU_REQ_FMT_16 = 0, 1      # device request records: pu_req, pu_req16
 
 PU_DSUM_BUCKETS = 32                     # delay summaries (pu_dsum_*)
+PU_DHIST_SUB_BITS, PU_DHIST_BUCKETS, PU_DHIST_MAX_Q = 5, 864, 8     # log-linear delay histograms (pu_dhist_*)
 
 PU_ERRF_CORE_RANGE = 1 << 0
 PU_ERRF_WB_MISS = 1 << 1
@@ -129,6 +130,10 @@ class DsumReplica(C.Structure):         # pu_dsum_replica
     _fields_ = [("cls", DsumClass * 2), ("core_out_of_range", C.c_uint64)]
 
 
+class DhistQuantile(C.Structure):       # pu_dhist_quantile
+    _fields_ = [("count", C.c_uint64), ("bucket", C.c_int32 * PU_DHIST_MAX_Q)]
+
+
 class DresReplica(C.Structure):         # pu_dres_replica
     _fields_ = [
         ("stats", Stats), ("processed", C.c_uint64), ("halted", C.c_int32), ("cores_done", C.c_int32),
@@ -170,6 +175,9 @@ DSUM_CLASS_DTYPE = np.dtype([("count", "<u8"), ("sum", "<i8"), ("min", "<i4"), (
                              ("hist", "<u8", (PU_DSUM_BUCKETS,))])
 DSUM_DTYPE = np.dtype([("cls", DSUM_CLASS_DTYPE, (2,)), ("core_out_of_range", "<u8")])
 assert DSUM_DTYPE.itemsize == C.sizeof(DsumReplica) == 568
+# pu_dhist_quantile as a numpy structured dtype
+DHIST_Q_DTYPE = np.dtype([("count", "<u8"), ("bucket", "<i4", (PU_DHIST_MAX_Q,))])
+assert DHIST_Q_DTYPE.itemsize == C.sizeof(DhistQuantile) == 40
 # pu_level_stats / pu_stats / pu_dres_replica as numpy structured dtypes
 LEVEL_STATS_DTYPE = np.dtype([("ins", "<u8"), ("miss", "<u8"), ("evict", "<u8"), ("wb", "<u8")])
 STATS_DTYPE = np.dtype(

@@ -131,6 +131,18 @@ def lib() -> C.CDLL:
         "pu_dsum_host_init": (None, [P(A.DsumReplica)]),
         "pu_dsum_host_add": (C.c_int, [P(A.DsumReplica), P(C.c_uint64), P(C.c_int64), C.c_int, C.c_void_p, C.c_int,
                                        P(C.c_int32), C.c_size_t]),
+        "pu_dhist_open": (C.c_void_p, [C.c_int, C.c_int]),
+        "pu_dhist_close": (None, [C.c_void_p]),
+        "pu_dhist_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "pu_dhist_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(C.c_uint64)]),
+        "pu_dhist_quantiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(C.c_uint32), C.c_int, P(A.DhistQuantile)]),
+        "pu_dhist_read_total": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(C.c_uint64)]),
+        "pu_dhist_reset": (C.c_int, [C.c_void_p]),
+        "pu_dhist_state_bytes": (C.c_uint64, [C.c_void_p]),
+        "pu_dhist_host_add": (C.c_int, [P(C.c_uint64), C.c_void_p, C.c_int, P(C.c_int32), C.c_size_t]),
+        "pu_dhist_host_quantiles": (C.c_int, [P(C.c_uint64), P(C.c_uint32), C.c_int, P(C.c_uint64), P(C.c_int32)]),
+        "pu_dhist_bucket_of": (C.c_int, [C.c_int32]),
+        "pu_dhist_bucket_bounds": (C.c_int, [C.c_int, P(C.c_int32), P(C.c_int32)]),
         "pu_dres_open": (C.c_void_p, [C.c_void_p, C.c_int]),
         "pu_dres_close": (None, [C.c_void_p]),
         "pu_dres_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -483,6 +495,132 @@ class DeviceDelaySummary(_Owner):
         rc = lib().pu_dsum_reset(self._handle())
         if rc != 0:
             raise UncoreError(f"pu_dsum_reset: {last_error()} ({rc})")
+
+
+# ---------------------------------------------------------------- delay histograms
+def _ppm_array(ppm) -> np.ndarray:
+    """Quantiles in parts per million as the uint32 array the library takes (it checks count and range)."""
+    a = np.atleast_1d(np.asarray(ppm, dtype=np.int64))
+    if a.ndim != 1 or (a < 0).any() or (a > 0xFFFFFFFF).any():
+        raise UncoreError("quantiles: ppm is a list of integers in [0, 1000000]")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def dhist_bucket_of(d: int) -> int:
+    """The log-linear bucket of a delay (pu_dhist_bucket_of; the rule is in include/primeuncore.h)."""
+    return int(lib().pu_dhist_bucket_of(int(d)))
+
+
+def dhist_bucket_bounds(k: int) -> tuple[int, int]:
+    """(lo, hi), both inclusive, of the delays bucket k holds (pu_dhist_bucket_bounds)."""
+    lo, hi = C.c_int32(), C.c_int32()
+    rc = lib().pu_dhist_bucket_bounds(int(k), C.byref(lo), C.byref(hi))
+    if rc != 0:
+        raise UncoreError(f"pu_dhist_bucket_bounds: {last_error()} ({rc})")
+    return lo.value, hi.value
+
+
+def delay_histogram(reqs: np.ndarray, delays: np.ndarray, fmt: int = A.PU_REQ_FMT_32) -> np.ndarray:
+    """The host fold of (request, delay) pairs into a [2, PU_DHIST_BUCKETS] uint64 log-linear
+    histogram, reads and writes apart (pu_dhist_host_add).  reqs as for summarize_delays.
+    Needs no device."""
+    n = len(delays)
+    if fmt == A.PU_REQ_FMT_16:
+        assert reqs.dtype == np.uint64 and reqs.shape == (n, 2)
+    else:
+        assert reqs.dtype == A.REQ_DTYPE and reqs.shape == (n,)
+    reqs = np.ascontiguousarray(reqs)
+    delays = np.ascontiguousarray(delays, dtype=np.int32)
+    out = np.zeros((2, A.PU_DHIST_BUCKETS), dtype=np.uint64)
+    rc = lib().pu_dhist_host_add(_as(out, C.c_uint64), reqs.ctypes.data, fmt, _as(delays, C.c_int32), n)
+    if rc != 0:
+        raise UncoreError(f"pu_dhist_host_add: {last_error()} ({rc})")
+    return out
+
+
+def histogram_quantiles(hist: np.ndarray, ppm) -> tuple[np.ndarray, np.ndarray]:
+    """(count, bucket) of log-linear histograms [..., PU_DHIST_BUCKETS]: per histogram its count
+    (uint64 [...]) and the bucket of every quantile of ppm (int32 [..., len(ppm)]; -1 for an
+    empty histogram), by the nearest-rank rule (pu_dhist_host_quantiles).  Needs no device."""
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    if h.ndim < 1 or h.shape[-1] != A.PU_DHIST_BUCKETS:
+        raise UncoreError(f"histogram_quantiles: the last axis holds {A.PU_DHIST_BUCKETS} buckets")
+    q = _ppm_array(ppm)
+    flat = h.reshape(-1, A.PU_DHIST_BUCKETS)
+    count = np.zeros(len(flat), dtype=np.uint64)
+    bucket = np.full((len(flat), max(len(q), 1)), -1, dtype=np.int32)
+    for i in range(len(flat)):
+        rc = lib().pu_dhist_host_quantiles(_as(flat[i], C.c_uint64), _as(q, C.c_uint32), len(q),
+                                           _as(count[i:], C.c_uint64), _as(bucket[i], C.c_int32))
+        if rc != 0:
+            raise UncoreError(f"pu_dhist_host_quantiles: {last_error()} ({rc})")
+    return count.reshape(h.shape[:-1]), bucket.reshape(h.shape[:-1] + (bucket.shape[1],))
+
+
+class DeviceDelayHistogram(_Owner):
+    """Per-replica log-linear delay histograms kept on the device (pu_dhist_*): `add` counts
+    every replica's records [begin[r], end[r]) of device request and delay arrays into its
+    [2, PU_DHIST_BUCKETS] histogram, bit for bit what delay_histogram gives; `quantiles`
+    and `total` are formed on the device.  Pointers are plain integers (tensor.data_ptr()).
+    Needs a GPU: there is no host fallback."""
+    _close, _no_handle = "pu_dhist_close", "DeviceDelayHistogram is closed"
+
+    def __init__(self, count: int, device: int = 0):
+        self._n = count
+        h = lib().pu_dhist_open(count, device)
+        if not h:
+            raise UncoreError(f"pu_dhist_open: {last_error()}")
+        self._h = h
+
+    def __len__(self) -> int:
+        return self._n
+
+    state_bytes = _state_bytes("pu_dhist_state_bytes", "Device memory the set holds.")
+
+    def add(self, d_reqs_ptr: int, d_delay_ptr: int, d_begin_ptr: int, d_end_ptr: int, fmt: int = A.PU_REQ_FMT_32,
+            stream_ptr: int = 0) -> None:
+        """As DeviceDelaySummary.add: asynchronous on stream_ptr (0 is the set's own stream);
+        d_begin / d_end: device uint64, one entry per replica, in records."""
+        rc = lib().pu_dhist_add(self._handle(), d_reqs_ptr or None, fmt, d_delay_ptr or None, d_begin_ptr or None,
+                                d_end_ptr or None, stream_ptr or None)
+        if rc != 0:
+            raise UncoreError(f"pu_dhist_add: {last_error()} ({rc})")
+
+    def read(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Histograms of replicas [first, first + n): uint64 [n, 2, PU_DHIST_BUCKETS] (waits for the set's calls)."""
+        n = self._n - first if n is None else n
+        out = np.zeros((max(n, 0), 2, A.PU_DHIST_BUCKETS), dtype=np.uint64)
+        rc = lib().pu_dhist_read(self._handle(), first, n, _as(out, C.c_uint64))
+        if rc != 0:
+            raise UncoreError(f"pu_dhist_read: {last_error()} ({rc})")
+        return out
+
+    def quantiles(self, ppm, first: int = 0, n: Optional[int] = None) -> tuple[np.ndarray, np.ndarray]:
+        """(count, bucket) of replicas [first, first + n), formed on the device: count uint64 [n, 2],
+        bucket int32 [n, 2, len(ppm)] (-1 for an empty class); ppm: up to PU_DHIST_MAX_Q quantiles
+        in parts per million.  dhist_bucket_bounds gives the delays a bucket holds."""
+        n = self._n - first if n is None else n
+        q = _ppm_array(ppm)
+        out = np.zeros((max(n, 0), 2), dtype=A.DHIST_Q_DTYPE)
+        rc = lib().pu_dhist_quantiles(self._handle(), first, n, _as(q, C.c_uint32), len(q), _as(out, A.DhistQuantile))
+        if rc != 0:
+            raise UncoreError(f"pu_dhist_quantiles: {last_error()} ({rc})")
+        return out["count"].copy(), out["bucket"][:, :, :len(q)].copy()
+
+    def total(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """The histogram summed over replicas [first, first + n): uint64 [2, PU_DHIST_BUCKETS].
+        Histograms add elementwise, so ranks sum what this returns."""
+        n = self._n - first if n is None else n
+        out = np.zeros((2, A.PU_DHIST_BUCKETS), dtype=np.uint64)
+        rc = lib().pu_dhist_read_total(self._handle(), first, n, _as(out, C.c_uint64))
+        if rc != 0:
+            raise UncoreError(f"pu_dhist_read_total: {last_error()} ({rc})")
+        return out
+
+    def reset(self) -> None:
+        rc = lib().pu_dhist_reset(self._handle())
+        if rc != 0:
+            raise UncoreError(f"pu_dhist_reset: {last_error()} ({rc})")
 
 
 QUEUE_KINDS = ("x", "y", "z", "bus")     # pu_config_queue_ends: kind 0 .. 3

@@ -16,6 +16,14 @@ last chunk (DeviceRunResults.gather on the same stream; 448 B per replica more):
 replica's line gains a "results" object -- requests, the simulated end cycle, link
 visits, the busiest link with its two ends, network and DRAM counters -- and one last
 line lists the ensemble's ten busiest links, by visits summed over the replicas.
+
+With --quantiles a log-linear delay histogram is kept on the device as well
+(DeviceDelayHistogram.add on the same stream, after the summary's add; 13,824 B per
+replica): every replica's "read" and "write" objects gain "p50", "p90", "p99" and
+"p999", each {"ge": lo, "le": hi}, the bounds of the histogram bucket that holds the
+quantile (exact below 64 cycles, within 3.2 % above; null for an empty class), read
+from the histogram on the device, and one last line carries the same for the histogram
+summed over the replicas.
 """
 from __future__ import annotations
 
@@ -58,6 +66,31 @@ def replica_line(r: int, seed: int, s, flags: int) -> dict:
     line["core_out_of_range"] = int(s["core_out_of_range"])
     line["error_flags"] = flags
     return line
+
+
+QUANTILES = (("p50", 500000), ("p90", 900000), ("p99", 990000), ("p999", 999000))     # name, parts per million
+QUANTILE_PPM = [ppm for _, ppm in QUANTILES]
+
+
+def quantile_object(buckets) -> dict:
+    """One class's answering buckets of QUANTILES (histogram_quantiles / DeviceDelayHistogram.quantiles)
+    as {"p50": {"ge": lo, "le": hi}, ...}; null for the -1 of an empty class."""
+    import primesim_amd as P
+    out = {}
+    for (name, _), b in zip(QUANTILES, buckets):
+        if int(b) < 0:
+            out[name] = None
+        else:
+            lo, hi = P.dhist_bucket_bounds(int(b))
+            out[name] = {"ge": lo, "le": hi}
+    return out
+
+
+def total_line(replicas: int, counts, buckets) -> dict:
+    """The last line of --quantiles: the quantiles of the histogram summed over the replicas, per class."""
+    return {"replicas": replicas,
+            "quantiles": {name: {"count": int(counts[c]), **quantile_object(buckets[c])}
+                          for c, name in enumerate(("read", "write"))}}
 
 
 def link_entry(cfg, q: int, visits: int, block_visits=None) -> dict:
@@ -104,6 +137,8 @@ def main() -> int:
     ap.add_argument("--seed-base", type=int, default=1, help="replica r streams with seed seed-base + r")
     ap.add_argument("--fmt", type=int, choices=(32, 16), default=32, help="device request records: pu_req or pu_req16")
     ap.add_argument("--results", action="store_true", help="also gather the end-of-run results on the device")
+    ap.add_argument("--quantiles", action="store_true",
+                    help="also keep a log-linear delay histogram on the device and print p50 / p90 / p99 / p99.9")
     args = ap.parse_args()
 
     import torch
@@ -137,7 +172,8 @@ def main() -> int:
     dss = P.DeviceStreamSet(specs)
     dsum = P.DeviceDelaySummary(R, num_cores=[nc] * R)
     dres = P.DeviceRunResults(um) if args.results else None
-    records = totals = None
+    dhist = P.DeviceDelayHistogram(R) if args.quantiles else None
+    records = totals = qbuckets = total = None
     nlinks = 0
     try:
         for prog, th in P.stream_threads(specs[0]):
@@ -147,6 +183,9 @@ def main() -> int:
             dss.next_into(d_reqs.data_ptr(), n, fmt=fmt, stream_ptr=sp)
             um.run_device(d_reqs.data_ptr(), d_off.data_ptr(), d_del.data_ptr(), sp)
             dsum.add(d_reqs.data_ptr(), d_del.data_ptr(), d_off.data_ptr(), d_off.data_ptr() + 8, fmt=fmt, stream_ptr=sp)
+            if dhist is not None:
+                dhist.add(d_reqs.data_ptr(), d_del.data_ptr(), d_off.data_ptr(), d_off.data_ptr() + 8, fmt=fmt,
+                          stream_ptr=sp)
         if dres is not None:
             dres.gather(stream_ptr=sp)                                  # one launch, after the last chunk
         summaries = dsum.read()                                         # waits for the last add
@@ -154,6 +193,9 @@ def main() -> int:
             records = dres.read()                                       # waits for the gather
             totals = dres.queue_totals()
             nlinks = dres.num_links
+        if dhist is not None:
+            _, qbuckets = dhist.quantiles(QUANTILE_PPM)                 # waits for the last add
+            total = P.histogram_quantiles(dhist.total(), QUANTILE_PPM)
         stream.synchronize()
         if int(dss.positions().min()) != n * args.chunks:
             print("ensemble_summary: a stream ended before its last chunk", file=sys.stderr)
@@ -162,16 +204,23 @@ def main() -> int:
     finally:
         if dres is not None:
             dres.close()
+        if dhist is not None:
+            dhist.close()
         dsum.close()
         dss.close()
         um.close()
     for r in range(R):
         line = replica_line(r, args.seed_base + r, summaries[r], int(flags[r]))
+        if qbuckets is not None:
+            for c, name in enumerate(("read", "write")):
+                line[name].update(quantile_object(qbuckets[r][c]))
         if records is not None:
             line["results"] = results_object(cfg, records[r])
         print(json.dumps(line))
     if records is not None:
         print(json.dumps({"replicas": R, "hottest_links": hottest_links(cfg, totals[0], totals[1], nlinks)}))
+    if total is not None:
+        print(json.dumps(total_line(R, total[0], total[1])))
     return 0
 
 
