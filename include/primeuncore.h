@@ -748,6 +748,58 @@ int      pu_dres_host_gather(pu_handle* h, int replica, pu_dres_replica* out,
                              uint64_t* n_out, uint64_t* n1_out, size_t cap);
 int      pu_config_queue_ends(const pu_sim_cfg* cfg, int q, int* kind, int* a, int* b);
 
+/* Forking a warmed replica and its request stream (no reference counterpart; for ensembles
+ * that would otherwise simulate the same cold start once per replica: warm one replica,
+ * then branch it).
+ *
+ * pu_replica_fork: replicas [first, first + n) of h become bit-for-bit copies of replica
+ * src, as the arena holds it when the call's work runs on hip_stream (NULL = the engine's
+ * own stream, as for pu_run_device).  Asynchronous: the caller orders it against its runs
+ * by the stream, as for pu_run_device.  src inside the range is skipped and left as it is
+ * (so src = 0, first = 0, n = num_replicas is legal); n == 0 is a successful no-op.  The
+ * copy is the whole replica: cache and directory lines, the sharer pool and its free
+ * stack, queue headers and rings, TLBs and the page map, the counters with the error
+ * flags, completion cycles, the run state (an open message's running delay, halted, the
+ * limit position), the closed-loop core shifts and the DRAM banks.  A destination's
+ * pu_stats_get, pu_report, pu_core_completion, pu_error_flags, pu_limit_positions and
+ * pu_dres_* records therefore equal the source's right after the fork: they include the
+ * warm-up's counts, and a caller who wants the figures of the measured part alone
+ * subtracts the source's figures as of the fork.  A running resident kernel is joined first
+ * (the source's queue headers are then in device memory).  If src has its own thread
+ * scheduler (pu_*_core_replica) every destination gets a copy of it; otherwise a
+ * destination's own copy is dropped and it reads the shared one, as src does.  d_pos and
+ * d_sched of the sliced and pool launches are the caller's: a forked destination starts
+ * wherever the caller's d_pos says.  By default one kernel reads the source in 16-KiB
+ * tiles and stores each tile to every destination; PU_FORK_BY_COPIES does the same by one
+ * device-to-device copy per destination on the same stream.  Forks share their warm-up:
+ * they are correlated until their own streams have displaced it.
+ * Before anything is launched: PU_EINVAL for a NULL handle, a negative argument or
+ * unknown flags; PU_ERANGE for src or the range outside [0, num_replicas).
+ *
+ * pu_stream_fork / pu_dstream_fork: the stream that goes with a forked replica.  A fresh
+ * stream starts at cycle 0, in the past of a warmed replica, so the destination takes
+ * from the source its cursor (quantum, core, requests in the open message, position) and
+ * limit, every core's cycle and streaming position and, for PU_STREAM_SHARED_UNIFORM,
+ * the re-use ring with its counters.  Without reseeding (reseed == 0; seeds == NULL) the
+ * per-core generator states are copied too and the destination continues the source's
+ * stream byte for byte.  With reseeding core k's generator state becomes seed * 2^32 + k,
+ * the state a stream opened with that seed starts from, and the destination's seed
+ * parameter becomes seed; nothing else changes.  So a fork at position 0 is the fresh
+ * stream of the new seed, and positions and max_requests go on counting from the source's
+ * position.  pu_dstream_fork: streams [first, first + n) of the set from stream src of
+ * the same set, seeds[i] (host memory) for stream first + i; src inside the range is left
+ * as it is and its entry ignored; asynchronous on hip_stream and ordered with the set's
+ * other calls like pu_dstream_next.  A destination whose parameters differ from the
+ * source's in any field but the seed is refused with PU_EINVAL and a message naming the
+ * stream (its arrays are sized for its own shape), on the host, before anything is
+ * launched or changed.  pu_stream_fits_req16 does not depend on the seed, so a set's
+ * format-16 verdict stands.  PU_EINVAL for a NULL stream or set or a negative argument,
+ * PU_ERANGE for src or the range outside the set. */
+#define PU_FORK_BY_COPIES 1   /* the same result by one device-to-device copy per destination */
+int pu_replica_fork(pu_handle* h, int src, int first, int n, int flags, void* hip_stream);
+int pu_stream_fork(pu_stream* dst, const pu_stream* src, int reseed, uint64_t seed);
+int pu_dstream_fork(pu_dstream* s, int src, int first, int n, const uint64_t* seeds, void* hip_stream);
+
 /* Log-linear delay histograms kept on the device (no reference counterpart; a stage beside
  * pu_dsum_add on the same stream: pu_dstream_next -> pu_run_device -> pu_dsum_add ->
  * pu_dhist_add).  The 32 power-of-two buckets of pu_dsum_replica place a quantile within a

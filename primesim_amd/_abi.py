@@ -197,6 +197,7 @@ DRES_DTYPE = np.dtype([
 assert STATS_DTYPE.itemsize == C.sizeof(Stats) == 352
 assert DRES_DTYPE.itemsize == C.sizeof(DresReplica) == 448
 PU_DRES_QUEUES = 1                       # pu_dres_open: keep the per-queue map
+PU_FORK_BY_COPIES = 1                    # pu_replica_fork: one device-to-device copy per destination
 assert C.sizeof(SimCfg) == 24 + C.sizeof(SysCfg)
 
 

@@ -34,14 +34,20 @@ int limit_positions(pu_handle* h, uint64_t* out, size_t n);
 
 // What another translation unit may see of a handle (pu_handle is uncore.cpp's):
 // the arena of its R replicas, the geometry (on the host), its device, and the
-// mutex that guards its launches.
+// mutex that guards its launches, and its own stream (a hipStream_t; this header
+// does not include HIP).
 struct HandleView {
     char* arena;
     const Geo* geo;
     int R, device;
     std::mutex* mu;
+    void* stream;
 };
 HandleView handle_view(pu_handle* h);
+// The thread-scheduler side of pu_replica_fork: replicas [first, first + n) but
+// src get a copy of src's own scheduler, or lose theirs when src reads the
+// shared one.  The caller holds the handle's mutex and has checked the range.
+void handle_fork_sched(pu_handle* h, int src, int first, int n);
 // Joins the handle's resident kernel, if one runs: its queue headers are in
 // device memory afterwards.  The caller holds the handle's mutex.
 int handle_resident_stop(pu_handle* h);

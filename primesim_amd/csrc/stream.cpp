@@ -70,7 +70,7 @@ struct StreamGen {
         p = *pp;
         wpct = p.write_pct >= 0 ? p.write_pct : default_write_pct(p.kind);
         gens.assign((size_t)p.num_cores, CoreGen{});
-        for (int k = 0; k < p.num_cores; k++) gens[(size_t)k].rng.s = p.seed * 0x100000000ull + (uint64_t)k;
+        for (int k = 0; k < p.num_cores; k++) gens[(size_t)k].rng.s = seed_state(p.seed, k);
         limit = p.max_requests > 0 ? p.max_requests : INT64_MAX;
     }
 
@@ -182,6 +182,21 @@ int64_t pu_stream_next(pu_stream* s, pu_req* out, size_t n) {
 }
 
 int64_t pu_stream_position(const pu_stream* s) { return s ? s->g.n : PU_EINVAL; }
+
+// The rule is stream_step.h's (fork_cursor, fork_rng); the device set runs the same.
+int pu_stream_fork(pu_stream* dst, const pu_stream* src, int reseed, uint64_t seed) {
+    if (!dst || !src) return pu::set_error(PU_EINVAL, "pu_stream_fork: no stream");
+    if (dst == src) return 0;   // the source is left as it is
+    if (!fork_params_match(dst->g.p, src->g.p))
+        return pu::set_error(PU_EINVAL, "pu_stream_fork: the destination stream's parameters differ from the source's "
+                                        "in more than the seed");
+    StreamGen& d = dst->g;
+    const StreamGen& s = src->g;
+    d.gens = s.gens;   // cycles, streaming positions, rings; same num_cores
+    for (int k = 0; k < d.p.num_cores; k++) d.gens[(size_t)k].rng.s = fork_rng(s.gens[(size_t)k].rng.s, reseed != 0, seed, k);
+    fork_cursor(d, s, reseed != 0, seed);
+    return 0;
+}
 
 int64_t pu_stream_next_many(pu_stream* const* s, int count, pu_req* out, size_t n_each, size_t stride,
                             int threads) {

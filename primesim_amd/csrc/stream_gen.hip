@@ -11,6 +11,7 @@
 //   per core  three arrays over all cores of all streams, a stream's cores
 //             contiguous (lane = core loads and stores are contiguous):
 //             rng state, cycle, streaming position -- 24 B per core
+//   seeds     one word per stream: where pu_dstream_fork puts the new seeds
 //   rings     for PU_STREAM_SHARED_UNIFORM streams only: the 16-entry re-use
 //             ring as [16][cores] plus one word per core holding its two counters
 //
@@ -75,6 +76,8 @@ struct DevGen {
 
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
+__device__ __forceinline__ size_t round16_dev(size_t v) { return (v + 15) & ~(size_t)15; }
+
 template <int FMT>
 __device__ __forceinline__ void store_record(void* out, size_t idx, uint64_t addr, int64_t timer, int core, int prog,
                                              uint8_t type, bool batch_start) {
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void dstream_init_kernel(const DsHdr* hdr
     const uint64_t seed = H->p.seed, core0 = H->core0, ring_off = H->ring_off;
     uint32_t* ctr = ring_off ? (uint32_t*)(base + ring_off + (size_t)16 * 8 * (size_t)cores) : nullptr;
     for (int k = (int)threadIdx.x; k < cores; k += kThreads) {
-        rng[core0 + k] = seed * 0x100000000ull + (uint64_t)k;
+        rng[core0 + k] = seed_state(seed, k);
         cyc[core0 + k] = 0;
         spos[core0 + k] = 0;
         if (ctr) ctr[k] = 0;
@@ -222,11 +225,49 @@ __global__ __launch_bounds__(kThreads) void dstream_next_kernel(DsHdr* hdrs, uin
     }
 }
 
+// pu_dstream_fork: one workgroup per destination first + blockIdx.x (the source
+// itself leaves at once), lanes are cores.  The three per-core arrays go by
+// contiguous loads and stores, the generator state through fork_rng; the ring
+// block of a PU_STREAM_SHARED_UNIFORM stream (the same size in both: the host
+// has compared the parameters) by 16-B pieces; one lane writes the header's
+// cursor, limit and seed (stream_step.h: fork_cursor).  seeds: device memory,
+// seeds[i] for stream first + i, or NULL for exact clones.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(kThreads) void dstream_fork_kernel(DsHdr* hdrs, uint8_t* base, uint64_t* rng, int64_t* cyc,
+                                                                 uint64_t* spos, int src, int first,
+                                                                 const uint64_t* seeds) {
+    const int d = first + (int)blockIdx.x;
+    if (d == src) return;
+    const DsHdr* const S = hdrs + src;
+    DsHdr* const D = hdrs + d;
+    const int cores = S->p.num_cores;
+    const uint64_t s0 = S->core0, d0 = D->core0, s_ring = S->ring_off, d_ring = D->ring_off;
+    const bool reseed = seeds != nullptr;
+    const uint64_t seed = reseed ? seeds[blockIdx.x] : 0;
+    for (int k = (int)threadIdx.x; k < cores; k += kThreads) {
+        rng[d0 + k] = fork_rng(rng[s0 + k], reseed, seed, k);
+        cyc[d0 + k] = cyc[s0 + k];
+        spos[d0 + k] = spos[s0 + k];
+    }
+    if (s_ring && d_ring) {
+        const size_t pieces = round16_dev((size_t)cores * (16 * 8 + 4)) / 16;
+        const u32x4* const from = (const u32x4*)(base + s_ring);
+        u32x4* const to = (u32x4*)(base + d_ring);
+        for (size_t k = threadIdx.x; k < pieces; k += kThreads) to[k] = from[k];
+    }
+    if (threadIdx.x == 0) fork_cursor(*D, *S, reseed, seed);
+}
+
 }  // namespace
 
 struct pu_dstream : pu::DeviceSet {
     int count = 0;
     std::string refuse16;   // why the set has no format 16 ("" = every stream fits)
+    std::vector<pu_stream_params> params;   // as the device headers hold them (a fork compares them on the host)
+    uint64_t* d_seeds = nullptr;            // [count], in the set's allocation: a fork's seeds on the device
+    uint64_t* h_seeds = nullptr;            // [count], pinned: what the last fork's copy reads
+    bool seeds_in_flight = false;
     DsHdr* hdrs = nullptr;
     uint64_t* rng = nullptr;
     int64_t* cyc = nullptr;
@@ -250,7 +291,7 @@ pu_dstream* pu_dstream_open(const pu_stream_params* params, int count, int devic
     if (!s) return nullptr;
     s->count = count;
 
-    // layout: headers | rng | cycle | streaming position | ring blocks
+    // layout: headers | rng | cycle | streaming position | fork seeds | ring blocks
     std::vector<DsHdr> hdrs((size_t)count);
     size_t cores = 0;
     for (int i = 0; i < count; i++) {
@@ -267,7 +308,8 @@ pu_dstream* pu_dstream_open(const pu_stream_params* params, int count, int devic
     const size_t off_rng = round16((size_t)count * sizeof(DsHdr));
     const size_t off_cyc = off_rng + round16(cores * 8);
     const size_t off_pos = off_cyc + round16(cores * 8);
-    size_t bytes = off_pos + round16(cores * 8);
+    const size_t off_seeds = off_pos + round16(cores * 8);
+    size_t bytes = off_seeds + round16((size_t)count * 8);
     for (DsHdr& h : hdrs)
         if (h.p.kind == PU_STREAM_SHARED_UNIFORM) {
             h.ring_off = bytes;
@@ -281,6 +323,8 @@ pu_dstream* pu_dstream_open(const pu_stream_params* params, int count, int devic
     s->rng = (uint64_t*)(s->base + off_rng);
     s->cyc = (int64_t*)(s->base + off_cyc);
     s->spos = (uint64_t*)(s->base + off_pos);
+    s->d_seeds = (uint64_t*)(s->base + off_seeds);
+    s->params.assign(params, params + count);
     if (hipMemcpyAsync(s->hdrs, hdrs.data(), (size_t)count * sizeof(DsHdr), hipMemcpyHostToDevice, s->stream) != hipSuccess)
         return pu::drop_set(s, PU_EIO, "header upload failed");
     hipLaunchKernelGGL(dstream_init_kernel, dim3((unsigned)count), dim3(kThreads), 0, s->stream, s->hdrs, s->base, s->rng,
@@ -291,7 +335,58 @@ pu_dstream* pu_dstream_open(const pu_stream_params* params, int count, int devic
     return s;
 }
 
-void pu_dstream_close(pu_dstream* s) { pu::close_set(s); }
+void pu_dstream_close(pu_dstream* s) {
+    if (s && s->h_seeds) {
+        (void)hipSetDevice(s->device);
+        (void)s->wait_outstanding();
+        (void)hipHostFree(s->h_seeds);
+        s->h_seeds = nullptr;
+    }
+    pu::close_set(s);
+}
+
+int pu_dstream_fork(pu_dstream* s, int src, int first, int n, const uint64_t* seeds, void* hip_stream) {
+    if (!s) return pu::set_error(PU_EINVAL, "pu_dstream_fork: no set");
+    if (src < 0 || first < 0 || n < 0) return pu::set_error(PU_EINVAL, "pu_dstream_fork: negative argument");
+    if (src >= s->count) return pu::set_error(PU_ERANGE, "pu_dstream_fork: source stream out of range");
+    if ((int64_t)first + n > s->count) return pu::set_error(PU_ERANGE, "pu_dstream_fork: more streams than the set holds");
+    for (int d = first; d < first + n; d++)
+        if (d != src && !fork_params_match(s->params[(size_t)d], s->params[(size_t)src]))
+            return pu::set_error(PU_EINVAL, "pu_dstream_fork: the parameters of stream " + std::to_string(d) +
+                                                " differ from those of stream " + std::to_string(src) +
+                                                " in more than the seed");
+    if (n == 0 || (n == 1 && first == src)) return 0;
+    int rc = s->use();
+    if (rc) return rc;
+    if (seeds) {   // through the set's pinned buffer: the copy below is asynchronous, the caller's array is not ours
+        if (!s->h_seeds && hipHostMalloc((void**)&s->h_seeds, (size_t)s->count * 8, hipHostMallocDefault) != hipSuccess) {
+            s->h_seeds = nullptr;
+            (void)hipGetLastError();
+            return pu::set_error(PU_ENOMEM, "pu_dstream_fork: no pinned memory for the seeds");
+        }
+        if (s->seeds_in_flight) {   // an earlier fork's copy may still read the buffer
+            rc = s->wait_outstanding();
+            if (rc) return rc;
+            s->seeds_in_flight = false;
+        }
+        for (int i = 0; i < n; i++) s->h_seeds[i] = seeds[i];
+    }
+    hipStream_t st = s->pick(hip_stream);
+    rc = s->order_before(st);
+    if (rc) return rc;
+    if (seeds) {
+        if (hipMemcpyAsync(s->d_seeds, s->h_seeds, (size_t)n * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+            return pu::set_error(PU_EIO, "pu_dstream_fork: seed upload failed");
+        s->seeds_in_flight = true;
+    }
+    hipLaunchKernelGGL(dstream_fork_kernel, dim3((unsigned)n), dim3(kThreads), 0, st, s->hdrs, s->base, s->rng, s->cyc,
+                       s->spos, src, first, seeds ? (const uint64_t*)s->d_seeds : (const uint64_t*)nullptr);
+    rc = s->record_after(st, "pu_dstream_fork");
+    if (rc) return rc;
+    for (int i = 0; i < n; i++)   // the seeds the device headers now hold
+        if (first + i != src) s->params[(size_t)(first + i)].seed = seeds ? seeds[i] : s->params[(size_t)src].seed;
+    return 0;
+}
 
 int pu_dstream_next(pu_dstream* s, void* d_out, size_t n_each, size_t stride, int fmt, uint64_t* d_got,
                     void* hip_stream) {

@@ -209,4 +209,41 @@ PU_HD inline void cursor_advance(Cursor& cur, int group, int cut_lane, uint64_t 
     }
 }
 
+// ------------------------------------------------------------------------ fork
+// pu_stream_fork / pu_dstream_fork: the destination continues from the source's
+// position (a warmed replica's clocks stand at the source's cycles, not at 0)
+// with the source's random draws or, reseeded, with those of another seed.
+//   * cursor (q, c, in_msg, n) and limit: the source's;
+//   * every core's cycle and streaming position, and for
+//     PU_STREAM_SHARED_UNIFORM the re-use ring with its two counters: the
+//     source's (copied by the caller: plain copies);
+//   * a core's generator state: the source's, or seed_state(seed, k) reseeded;
+//   * params.seed: the source's, or `seed` reseeded; nothing else changes.
+
+// The generator state a stream of `seed` opens core k with.
+PU_HD inline uint64_t seed_state(uint64_t seed, int k) { return seed * 0x100000000ull + (uint64_t)k; }
+
+PU_HD inline uint64_t fork_rng(uint64_t src_state, bool reseed, uint64_t seed, int k) {
+    return reseed ? seed_state(seed, k) : src_state;
+}
+
+// The header's part; D and S have p, q, c, in_msg, n and limit (StreamGen, DsHdr).
+template <class D, class S>
+PU_HD inline void fork_cursor(D& d, const S& s, bool reseed, uint64_t seed) {
+    d.q = s.q;
+    d.c = s.c;
+    d.in_msg = s.in_msg;
+    d.n = s.n;
+    d.limit = s.limit;
+    d.p.seed = reseed ? seed : s.p.seed;
+}
+
+// A destination is sized for its own shape: it takes a fork only from a source
+// whose parameters equal its own in every field but the seed.
+inline bool fork_params_match(const pu_stream_params& a, const pu_stream_params& b) {
+    return a.kind == b.kind && a.num_cores == b.num_cores && a.quantum == b.quantum && a.num_quanta == b.num_quanta &&
+           a.max_msg == b.max_msg && a.num_progs == b.num_progs && a.max_requests == b.max_requests &&
+           a.write_pct == b.write_pct;
+}
+
 }  // namespace pu_stream_step

@@ -1158,7 +1158,12 @@ int pu::limit_positions(pu_handle* h, uint64_t* out, size_t n) {
 
 // The handle as the other device-side stages see it (common.h; run_results.hip).
 pu::HandleView pu::handle_view(pu_handle* h) {
-    return pu::HandleView{h->arena, &h->geo, h->R, h->device, &h->mu};
+    return pu::HandleView{h->arena, &h->geo, h->R, h->device, &h->mu, (void*)h->stream};
+}
+void pu::handle_fork_sched(pu_handle* h, int src, int first, int n) {
+    const pu::Sched* const own = h->rsched[(size_t)src].get();
+    for (int d = first; d < first + n; d++)
+        if (d != src) h->rsched[(size_t)d].reset(own ? new pu::Sched(*own) : nullptr);
 }
 int pu::handle_resident_stop(pu_handle* h) { return resident_stop(h); }
 int pu::config_geometry(const pu_sim_cfg* cfg, Geo* out) { return build_geo(cfg, out); }

@@ -14,6 +14,7 @@ without the built library raises — there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -121,6 +122,9 @@ def lib() -> C.CDLL:
                                       C.c_void_p]),
         "pu_dstream_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
         "pu_dstream_state_bytes": (C.c_uint64, [C.c_void_p]),
+        "pu_replica_fork": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "pu_stream_fork": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64]),
+        "pu_dstream_fork": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, P(C.c_uint64), C.c_void_p]),
         "pu_dsum_open": (C.c_void_p, [C.c_int, P(C.c_int32), C.c_int]),
         "pu_dsum_close": (None, [C.c_void_p]),
         "pu_dsum_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -301,6 +305,17 @@ def generate_stream(spec: StreamSpec) -> np.ndarray:
     return out
 
 
+def _fork_range(count: int, src: int, first: int, n: Optional[int], seeds):
+    """(first, n, seeds) of a fork over `count` members: n = None is "to the end"; seeds,
+    where given, one uint64 per member of the range."""
+    n = count - first if n is None else n
+    if seeds is not None:
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        if seeds.shape != (max(n, 0),):
+            raise UncoreError(f"fork: {seeds.shape} seeds for a range of {n}")
+    return first, n, seeds
+
+
 class StreamSet:
     """Resumable generators for several streams (pu_stream_open/next_many):
     `next(n)` returns the next n requests of every stream as an [count, n]
@@ -308,6 +323,7 @@ class StreamSet:
 
     def __init__(self, specs: list[StreamSpec]):
         self._h = []
+        self._specs = list(specs)
         for sp in specs:
             p = sp.params()
             h = lib().pu_stream_open(C.byref(p))
@@ -338,6 +354,30 @@ class StreamSet:
 
     def position(self, i: int = 0) -> int:
         return int(lib().pu_stream_position(self._h[i]))
+
+    def fork(self, src: int, first: int = 0, n: Optional[int] = None, seeds=None) -> None:
+        """Streams [first, first + n) continue from stream src's position (pu_stream_fork):
+        exact clones without seeds, else stream first + i draws as a stream of seeds[i]
+        does.  src inside the range is left as it is.  A stream whose parameters differ
+        from src's in more than the seed is refused, before any stream is changed."""
+        first, n, seeds = _fork_range(len(self._h), src, first, n, seeds)
+        if not (0 <= src < len(self._h) and 0 <= first and 0 <= n and first + n <= len(self._h)):
+            raise UncoreError(f"pu_stream_fork: source {src} or range [{first}, {first + n}) outside the set")
+        shape = dataclasses.replace(self._specs[src], seed=0)
+        for d in range(first, first + n):   # all or nothing: pu_stream_fork itself refuses stream by stream
+            if dataclasses.replace(self._specs[d], seed=0) != shape:
+                raise UncoreError(f"pu_stream_fork: the parameters of stream {d} differ from those of stream {src} "
+                                  "in more than the seed")
+        for i in range(n):
+            d = first + i
+            if d == src:
+                continue
+            seed = int(seeds[i]) if seeds is not None else 0
+            rc = lib().pu_stream_fork(self._h[d], self._h[src], int(seeds is not None), seed)
+            if rc != 0:
+                raise UncoreError(f"pu_stream_fork: stream {d}: {last_error()} ({rc})")
+            self._specs[d] = dataclasses.replace(self._specs[d], seed=seed if seeds is not None
+                                                 else self._specs[src].seed)
 
     def close(self) -> None:
         for h in self._h:
@@ -394,6 +434,16 @@ class DeviceStreamSet(_Owner):
                                    fmt, d_got_ptr or None, stream_ptr or None)
         if rc != 0:
             raise UncoreError(f"pu_dstream_next: {last_error()} ({rc})")
+
+    def fork(self, src: int, first: int = 0, n: Optional[int] = None, seeds=None, stream_ptr: int = 0) -> None:
+        """StreamSet.fork on the device (pu_dstream_fork), asynchronous on stream_ptr like
+        next_into: streams [first, first + n) continue from stream src's position, as exact
+        clones without seeds, else stream first + i with the draws of a stream of seeds[i]."""
+        first, n, seeds = _fork_range(self._n, src, first, n, seeds)
+        rc = lib().pu_dstream_fork(self._handle(), src, first, n, None if seeds is None else _as(seeds, C.c_uint64),
+                                   stream_ptr or None)
+        if rc != 0:
+            raise UncoreError(f"pu_dstream_fork: {last_error()} ({rc})")
 
     def positions(self) -> np.ndarray:
         """Requests produced so far per stream (waits for the set's outstanding calls)."""
@@ -952,6 +1002,19 @@ class UncoreManager(_Owner):
                                       slots, budget_us, stream_ptr or None)
         if rc != 0:
             raise UncoreError(f"run_device_pool: {last_error()}")
+
+    def fork_replica(self, src: int, first: int = 0, n: Optional[int] = None, by_copies: bool = False,
+                     stream_ptr: int = 0) -> None:
+        """Replicas [first, first + n) (n = None: to the last) become bit-for-bit copies of
+        replica src (pu_replica_fork), asynchronously on stream_ptr like run_device; src
+        inside the range is left as it is.  Their statistics, reports and completion cycles
+        are then the source's, warm-up included.  by_copies: one device-to-device copy per
+        destination instead of the kernel."""
+        n = self.replicas - first if n is None else n
+        rc = lib().pu_replica_fork(self._handle(), src, first, n, A.PU_FORK_BY_COPIES if by_copies else 0,
+                                   stream_ptr or None)
+        if rc != 0:
+            raise UncoreError(f"pu_replica_fork: {last_error()} ({rc})")
 
     def synchronize(self) -> None:
         if lib().pu_synchronize(self._handle()) != 0:

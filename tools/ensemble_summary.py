@@ -24,6 +24,14 @@ replica): every replica's "read" and "write" objects gain "p50", "p90", "p99" an
 quantile (exact below 64 cycles, within 3.2 % above; null for an empty class), read
 from the histogram on the device, and one last line carries the same for the histogram
 summed over the replicas.
+
+With --warmup-chunks K the cold start is simulated once: replica 0 alone runs K chunks of
+stream 0 (the other replicas get empty ranges; nothing goes to the summaries or
+histograms), then every other replica becomes a copy of it (UncoreManager.fork_replica)
+and every other stream continues from stream 0's position with its own seed
+(DeviceStreamSet.fork), all on the same stream, and the --chunks measured chunks run as
+usual.  The forks share their warm-up: they are correlated until their own streams have
+displaced it, and engine counters ("results", error flags) include the warm-up's.
 """
 from __future__ import annotations
 
@@ -139,6 +147,8 @@ def main() -> int:
     ap.add_argument("--results", action="store_true", help="also gather the end-of-run results on the device")
     ap.add_argument("--quantiles", action="store_true",
                     help="also keep a log-linear delay histogram on the device and print p50 / p90 / p99 / p99.9")
+    ap.add_argument("--warmup-chunks", type=int, default=0,
+                    help="warm replica 0 alone for this many chunks, then fork it and its stream to the others")
     args = ap.parse_args()
 
     import torch
@@ -155,7 +165,7 @@ def main() -> int:
     fmt, rec = (A.PU_REQ_FMT_16, 16) if args.fmt == 16 else (A.PU_REQ_FMT_32, 32)
     quantum = cfg.thread_sync_interval
     # a core issues at least quantum / 4 requests a quantum: enough quanta for every chunk
-    quanta = -(-n * args.chunks * 4 // (nc * quantum)) + 1
+    quanta = -(-n * (args.chunks + args.warmup_chunks) * 4 // (nc * quantum)) + 1
     specs = [P.StreamSpec(args.kind, nc, seed=args.seed_base + r, quantum=quantum, num_quanta=quanta,
                           max_msg=cfg.max_msg_size) for r in range(R)]
 
@@ -179,6 +189,14 @@ def main() -> int:
         for prog, th in P.stream_threads(specs[0]):
             um.allocCore(prog, th)
         um.set_device_req_format(fmt)
+        if args.warmup_chunks > 0:
+            d_warm = d_off.clamp(max=n)                                 # replica 0: [0, n); every other: empty
+            torch.cuda.synchronize(dev)                                 # made on torch's stream, read on ours
+            for _ in range(args.warmup_chunks):
+                dss.next_into(d_reqs.data_ptr(), n, fmt=fmt, stream_ptr=sp)
+                um.run_device(d_reqs.data_ptr(), d_warm.data_ptr(), d_del.data_ptr(), sp)
+            um.fork_replica(0, stream_ptr=sp)
+            dss.fork(0, seeds=[args.seed_base + r for r in range(R)], stream_ptr=sp)
         for _ in range(args.chunks):
             dss.next_into(d_reqs.data_ptr(), n, fmt=fmt, stream_ptr=sp)
             um.run_device(d_reqs.data_ptr(), d_off.data_ptr(), d_del.data_ptr(), sp)
@@ -197,7 +215,7 @@ def main() -> int:
             _, qbuckets = dhist.quantiles(QUANTILE_PPM)                 # waits for the last add
             total = P.histogram_quantiles(dhist.total(), QUANTILE_PPM)
         stream.synchronize()
-        if int(dss.positions().min()) != n * args.chunks:
+        if int(dss.positions().min()) != n * (args.chunks + args.warmup_chunks):
             print("ensemble_summary: a stream ended before its last chunk", file=sys.stderr)
             return 1
         flags = um.error_flags(R)
