@@ -1,8 +1,8 @@
 // common.h — host-side helpers shared by the C-ABI translation units.
 #pragma once
 
+#include <cstdint>
 #include <map>
-#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -13,8 +13,10 @@ struct Geo;   // geometry.h
 
 namespace pu {
 
-// Records a message for pu_last_error() and returns `code`.
+// Records a message for pu_last_error() and returns `code` (common.cpp).
 int set_error(int code, const std::string& msg);
+// The calling thread's last message.
+const std::string& last_error();
 
 // 0 when `device` is a HIP device of this machine, else PU_ENODEV with the
 // error "no HIP device available", followed by " (note)" where a note is given.
@@ -32,27 +34,23 @@ int run_device_flags(pu_handle* h, const pu_req* d_reqs, const uint64_t* d_off, 
 // PU_ERRF_LIMITS bit (UINT64_MAX: none).
 int limit_positions(pu_handle* h, uint64_t* out, size_t n);
 
-// What another translation unit may see of a handle (pu_handle is uncore.cpp's):
-// the arena of its R replicas, the geometry (on the host), its device, and the
-// mutex that guards its launches, and its own stream (a hipStream_t; this header
-// does not include HIP).
-struct HandleView {
-    char* arena;
-    const Geo* geo;
-    int R, device;
-    std::mutex* mu;
-    void* stream;
+// The geometry pu_create builds for cfg, validated (geometry.cpp): 0, or PU_E*
+// with the error text.  pool_cap > 0 bounds the sharer-bitmap pool's entries.
+// No device.
+int config_geometry(const pu_sim_cfg* cfg, Geo* out, uint64_t pool_cap = 0);
+
+// A replica's layout is laid down field after field, each aligned
+// (geometry.cpp; the network unit hook lays down a small one of its own).
+inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+struct Layout {
+    uint64_t cur = 0;
+    uint64_t take(uint64_t bytes, uint64_t align = 256) {
+        cur = align_up(cur, align);
+        uint64_t o = cur;
+        cur += bytes;
+        return o;
+    }
 };
-HandleView handle_view(pu_handle* h);
-// The thread-scheduler side of pu_replica_fork: replicas [first, first + n) but
-// src get a copy of src's own scheduler, or lose theirs when src reads the
-// shared one.  The caller holds the handle's mutex and has checked the range.
-void handle_fork_sched(pu_handle* h, int src, int first, int n);
-// Joins the handle's resident kernel, if one runs: its queue headers are in
-// device memory afterwards.  The caller holds the handle's mutex.
-int handle_resident_stop(pu_handle* h);
-// The geometry pu_create would build for cfg (0 or PU_E* with the error text); no device.
-int config_geometry(const pu_sim_cfg* cfg, Geo* out);
 
 // ThreadSched (reference src/thread_sched.cpp:55-91) with its quirks: the
 // first free core is taken, a busy core is marked with its prog id, a core is

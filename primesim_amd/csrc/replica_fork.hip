@@ -29,6 +29,7 @@
 #include "../../include/primeuncore.h"
 #include "common.h"
 #include "geometry.h"
+#include "handle.h"
 #include "replica_fork_step.h"
 
 using namespace pu_fork_step;
@@ -81,33 +82,32 @@ extern "C" int pu_replica_fork(pu_handle* h, int src, int first, int n, int flag
     if (flags & ~PU_FORK_BY_COPIES) return pu::set_error(PU_EINVAL, "pu_replica_fork: unknown flags");
     if (src < 0 || first < 0 || n < 0) return pu::set_error(PU_EINVAL, "pu_replica_fork: negative argument");
     if (!h) return pu::set_error(PU_EINVAL, "pu_replica_fork: no handle");
-    const pu::HandleView v = pu::handle_view(h);
-    if (src >= v.R) return pu::set_error(PU_ERANGE, "pu_replica_fork: source replica out of range");
-    if ((int64_t)first + n > v.R) return pu::set_error(PU_ERANGE, "pu_replica_fork: more replicas than the handle holds");
+    if (src >= h->R) return pu::set_error(PU_ERANGE, "pu_replica_fork: source replica out of range");
+    if ((int64_t)first + n > h->R) return pu::set_error(PU_ERANGE, "pu_replica_fork: more replicas than the handle holds");
     if (n == 0) return 0;
 
-    std::lock_guard<std::mutex> lk(*v.mu);
-    int rc = pu::handle_resident_stop(h);   // the source's queue headers leave the chip first
+    std::lock_guard<std::mutex> lk(h->mu);
+    int rc = pu::resident_stop(h);   // the source's queue headers leave the chip first
     if (rc) return rc;
-    pu::handle_fork_sched(h, src, first, n);
+    pu::fork_sched(h, src, first, n);
     if (dest_count(src, first, n) == 0) return 0;
-    if (hipSetDevice(v.device) != hipSuccess) return pu::set_error(PU_ENODEV, "hipSetDevice failed");
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)v.stream;
-    const uint64_t bytes = v.geo->replica_bytes;
+    if (hipSetDevice(h->device) != hipSuccess) return pu::set_error(PU_ENODEV, "hipSetDevice failed");
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    const uint64_t bytes = h->geo.replica_bytes;
 
     if (flags & PU_FORK_BY_COPIES) {
-        const char* const from = v.arena + (uint64_t)src * bytes;
+        const char* const from = h->arena + (uint64_t)src * bytes;
         for (int d = first; d < first + n; d++)
             if (dest_taken(d, src) &&
-                hipMemcpyAsync(v.arena + (uint64_t)d * bytes, from, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess)
+                hipMemcpyAsync(h->arena + (uint64_t)d * bytes, from, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess)
                 return pu::set_error(PU_EIO, "pu_replica_fork: copy to replica " + std::to_string(d) + " failed");
         return 0;
     }
     const dim3 grid((unsigned)tiles_of(bytes), (unsigned)groups_of(n));
     if (non_temporal_stores())
-        hipLaunchKernelGGL(replica_fork_kernel<true>, grid, dim3(kLanes), 0, st, v.arena, bytes, src, first, n, (int)grid.y);
+        hipLaunchKernelGGL(replica_fork_kernel<true>, grid, dim3(kLanes), 0, st, h->arena, bytes, src, first, n, (int)grid.y);
     else
-        hipLaunchKernelGGL(replica_fork_kernel<false>, grid, dim3(kLanes), 0, st, v.arena, bytes, src, first, n, (int)grid.y);
+        hipLaunchKernelGGL(replica_fork_kernel<false>, grid, dim3(kLanes), 0, st, h->arena, bytes, src, first, n, (int)grid.y);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return pu::set_error(PU_EIO, std::string("pu_replica_fork: launch failed: ") + hipGetErrorString(e));
     return 0;

@@ -8,7 +8,7 @@
 // A tile is kLanes x kPieces pieces of kPieceBytes: piece u of a tile is one
 // contiguous run of kLanes * kPieceBytes = 4 KiB, lane l moving its l-th 16
 // bytes, so the lanes of a wave read and write contiguous memory.  A replica is
-// a multiple of 4,096 bytes (uncore.cpp: build_geo), hence of a piece but not
+// a multiple of 4,096 bytes (geometry.cpp: pu::config_geometry), hence of a piece but not
 // of a tile: the last tile is masked piece by piece (piece_live).
 //
 // The destinations [first, first + n) are dealt to G = groups_of(n) groups:

@@ -48,7 +48,9 @@
 #include "common.h"
 #include "device_set.h"
 #include "geometry.h"
+#include "handle.h"
 #include "run_results_step.h"
+#include "stats_rule.h"
 
 using namespace pu_run_results;
 using pu::round16;
@@ -58,7 +60,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kUnroll = 4;          // queues / cores / replicas per lane and trip
-constexpr int kTabs = 6;            // EngineStats.lvl_cnt rows: levels 0-3, PU_CNT_DIR, PU_CNT_TLB
+constexpr int kTabs = pu::kStatRows;   // EngineStats.lvl_cnt rows: levels 0-3, PU_CNT_DIR, PU_CNT_TLB
 constexpr int kEsWords = (int)(sizeof(EngineStats) / 8);
 constexpr int kRecWords = (int)(sizeof(pu_dres_replica) / 8);
 constexpr int kGroups = 120;        // replica groups of the totals' first pass, at most
@@ -120,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void dres_gather_kernel(const char* __res
     __shared__ WavePart s_part[kWaves];
     __shared__ EngineStats s_es;
     __shared__ unsigned long long s_tab[kTabs][kWaves][4];
-    __shared__ unsigned long long s_lv[kTabs][4];
+    __shared__ uint64_t s_lv[kTabs][4];
     __shared__ pu_dres_replica s_rec;
 
     const int r = first + (int)blockIdx.x;
@@ -232,7 +234,7 @@ __global__ __launch_bounds__(kThreads) void dres_gather_kernel(const char* __res
     }
     __syncthreads();   // the partials, the tables' partials and EngineStats are in LDS
 
-    // lvl_cnt plus, for the tables summed above, the per-cache counters (pu_stats_get, uncore.cpp):
+    // lvl_cnt plus, for the tables summed above, the per-cache counters (pu_stats_get, report.cpp):
     // lane = row * 4 + counter
     if (tid < kTabs * 4) {
         const int k = tid >> 2, j = tid & 3;
@@ -245,34 +247,8 @@ __global__ __launch_bounds__(kThreads) void dres_gather_kernel(const char* __res
     __syncthreads();
 
     if (tid == 0) {
-        const EngineStats& es = s_es;
         pu_dres_replica& o = s_rec;
-        pu_stats& st = o.stats;
-        st.net_accesses = es.net_accesses;
-        st.net_distance = es.net_distance;
-        st.net_total_delay = es.net_total_delay;
-        st.net_router_delay = es.net_router_delay;
-        st.net_link_delay = es.net_link_delay;
-        st.net_inject_delay = es.net_inject_delay;
-        st.dram_accesses = es.dram_accesses;
-        st.total_bus_contention = es.total_bus_contention;
-        st.total_num_broadcast = es.total_num_broadcast;
-        st.num_levels = g.num_levels;
-        st._pad = 0;
-        for (int l = 0; l < PU_MAX_LEVELS; l++)
-            st.level[l] = l < g.num_levels ? pu_level_stats{s_lv[l][0], s_lv[l][1], s_lv[l][2], s_lv[l][3]} : pu_level_stats{0, 0, 0, 0};
-        st.directory = pu_level_stats{s_lv[PU_CNT_DIR][0], s_lv[PU_CNT_DIR][1], s_lv[PU_CNT_DIR][2], s_lv[PU_CNT_DIR][3]};
-        st.tlb = pu_level_stats{s_lv[PU_CNT_TLB][0], s_lv[PU_CNT_TLB][1], s_lv[PU_CNT_TLB][2], s_lv[PU_CNT_TLB][3]};
-        st.link_flits = es.link_flits;
-        st.mg1_calls = es.mg1_calls;
-        st.lockdown_calls = es.lockdown_calls;
-        st.bus_accesses = es.bus_accesses;
-        st.requests = es.requests;
-        st.error_flags = es.error_flags;
-        st.dram_row_hits = es.dram_row_hits;
-        st.dram_row_empty = es.dram_row_empty;
-        st.dram_row_conflicts = es.dram_row_conflicts;
-        st.dram_bank_wait = es.dram_bank_wait;
+        pu::stats_fill(o.stats, s_es, g.num_levels, s_lv);
 
         const RunState* const run = (const RunState*)(base + g.off_run);
         o.processed = run->processed;
@@ -386,7 +362,7 @@ DresGeo dres_geo(const Geo& g) {
     d.nqueues = g.nqueues;
     d.num_cores = g.num_cores;
     d.num_levels = g.num_levels;
-    if (!g.cnt_sum) {   // the tables pu_stats_get adds (uncore.cpp: read_replica)
+    if (!g.cnt_sum) {   // the tables pu_stats_get adds (report.cpp: read_replica)
         for (int l = 0; l < g.num_levels; l++) d.tab[d.ntabs++] = DresTab{g.lv[l].off_cnt, g.lv[l].ncaches, l};
         d.tab[d.ntabs++] = DresTab{g.dir.off_cnt, g.N, PU_CNT_DIR};
         if (g.tlb_enable) d.tab[d.ntabs++] = DresTab{g.tlb.off_cnt, g.num_cores, PU_CNT_TLB};
@@ -398,7 +374,6 @@ DresGeo dres_geo(const Geo& g) {
 
 struct pu_dres : pu::DeviceSet {
     pu_handle* h = nullptr;
-    pu::HandleView v{};
     DresGeo g{};
     bool map = false;
     int groups = 1;                 // slab rows allocated
@@ -408,16 +383,6 @@ struct pu_dres : pu::DeviceSet {
     uint64_t *slab_n = nullptr, *slab_n1 = nullptr;
     uint64_t *tot_n = nullptr, *tot_n1 = nullptr;
 };
-
-namespace {
-
-// The handle's queue headers are in device memory: its resident kernel has left.
-int quiesce(const pu::HandleView& v, pu_handle* h) {
-    std::lock_guard<std::mutex> lk(*v.mu);
-    return pu::handle_resident_stop(h);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -430,22 +395,20 @@ pu_dres* pu_dres_open(pu_handle* h, int flags) {
         pu::set_error(PU_EINVAL, "pu_dres_open: no handle (the results are gathered from a handle's replicas on its GPU)");
         return nullptr;
     }
-    const pu::HandleView v = pu::handle_view(h);
-    if (pu::device_check(v.device, "the device gather has no CPU fallback") != 0) return nullptr;
+    if (pu::device_check(h->device, "the device gather has no CPU fallback") != 0) return nullptr;
     pu_dres* s = pu::new_set<pu_dres>();
     if (!s) return nullptr;
     s->h = h;
-    s->v = v;
-    s->g = dres_geo(*v.geo);
+    s->g = dres_geo(h->geo);
     s->map = (flags & PU_DRES_QUEUES) != 0;
-    s->groups = v.R < kGroups ? v.R : kGroups;
+    s->groups = h->R < kGroups ? h->R : kGroups;
 
     // layout: records | map n | map n1 | slab n | slab n1 | totals n | totals n1
-    const size_t R = (size_t)v.R, nq = (size_t)s->g.nqueues;
+    const size_t R = (size_t)h->R, nq = (size_t)s->g.nqueues;
     const size_t map_b = s->map ? round16(R * nq * 8) : 0, slab_b = round16((size_t)s->groups * nq * 8), tot_b = round16(nq * 8);
     const size_t off_map = round16(R * sizeof(pu_dres_replica));
     const size_t off_slab = off_map + 2 * map_b, off_tot = off_slab + 2 * slab_b;
-    if (s->open(v.device, off_tot + 2 * tot_b, "pu_dres_open: the results of " + std::to_string(v.R) + " replicas (" +
+    if (s->open(h->device, off_tot + 2 * tot_b, "pu_dres_open: the results of " + std::to_string(h->R) + " replicas (" +
                                                   std::to_string(nq) + " queues each" + (s->map ? ", with the map)" : ")")) != 0)
         return pu::drop_set(s);
     s->rec = (pu_dres_replica*)s->base;
@@ -468,7 +431,7 @@ void pu_dres_close(pu_dres* s) { pu::close_set(s); }
 int pu_dres_gather(pu_dres* s, int first, int n, void* hip_stream) {
     if (!s) return pu::set_error(PU_EINVAL, "pu_dres_gather: no set");
     if (first < 0 || n < 0) return pu::set_error(PU_EINVAL, "pu_dres_gather: bad arguments");
-    if ((int64_t)first + n > s->v.R) return pu::set_error(PU_ERANGE, "more replicas than the handle holds");
+    if ((int64_t)first + n > s->h->R) return pu::set_error(PU_ERANGE, "more replicas than the handle holds");
     int rc = s->use();
     if (rc) return rc;
     if (n == 0) {   // nothing to launch: the totals of this gather are all zero
@@ -476,17 +439,17 @@ int pu_dres_gather(pu_dres* s, int first, int n, void* hip_stream) {
         s->last_n = 0;
         return 0;
     }
-    std::lock_guard<std::mutex> lk(*s->v.mu);   // as gather_error_flags: the headers leave the chip first
-    rc = pu::handle_resident_stop(s->h);
+    std::lock_guard<std::mutex> lk(s->h->mu);   // as gather_error_flags: the headers leave the chip first
+    rc = pu::resident_stop(s->h);
     if (rc) return rc;
     hipStream_t st = s->pick(hip_stream);
     rc = s->order_before(st);
     if (rc) return rc;
     if (s->map)
-        hipLaunchKernelGGL((dres_gather_kernel<true>), dim3((unsigned)n), dim3(kThreads), 0, st, s->v.arena, s->g, first,
+        hipLaunchKernelGGL((dres_gather_kernel<true>), dim3((unsigned)n), dim3(kThreads), 0, st, s->h->arena, s->g, first,
                            s->rec, s->map_n, s->map_n1);
     else
-        hipLaunchKernelGGL((dres_gather_kernel<false>), dim3((unsigned)n), dim3(kThreads), 0, st, s->v.arena, s->g, first,
+        hipLaunchKernelGGL((dres_gather_kernel<false>), dim3((unsigned)n), dim3(kThreads), 0, st, s->h->arena, s->g, first,
                            s->rec, (uint64_t*)nullptr, (uint64_t*)nullptr);
     rc = s->record_after(st, "pu_dres_gather");
     if (rc) return rc;
@@ -497,7 +460,7 @@ int pu_dres_gather(pu_dres* s, int first, int n, void* hip_stream) {
 
 int pu_dres_read(pu_dres* s, int first, int n, pu_dres_replica* out) {
     if (!s || first < 0 || n < 0 || (!out && n)) return pu::set_error(PU_EINVAL, "pu_dres_read: bad arguments");
-    if ((int64_t)first + n > s->v.R) return pu::set_error(PU_ERANGE, "more replicas than the handle holds");
+    if ((int64_t)first + n > s->h->R) return pu::set_error(PU_ERANGE, "more replicas than the handle holds");
     if (n == 0) return 0;
     return s->read_back(
         [&](hipStream_t st) {
@@ -510,7 +473,7 @@ int pu_dres_read(pu_dres* s, int first, int n, pu_dres_replica* out) {
 int pu_dres_read_queues(pu_dres* s, int replica, uint64_t* n_out, uint64_t* n1_out, size_t cap) {
     if (!s || replica < 0) return pu::set_error(PU_EINVAL, "pu_dres_read_queues: bad arguments");
     if (!s->map) return pu::set_error(PU_ENOTSUP, "pu_dres_read_queues: the set was opened without PU_DRES_QUEUES");
-    if (replica >= s->v.R) return pu::set_error(PU_ERANGE, "more replicas than the handle holds");
+    if (replica >= s->h->R) return pu::set_error(PU_ERANGE, "more replicas than the handle holds");
     const size_t nq = (size_t)s->g.nqueues;
     if (cap < nq) return pu::set_error(PU_ERANGE, "pu_dres_read_queues: room for fewer queues than a replica has");
     if (nq == 0 || (!n_out && !n1_out)) return 0;
@@ -536,7 +499,7 @@ int pu_dres_read_queue_totals(pu_dres* s, uint64_t* n_out, uint64_t* n1_out, siz
         return 0;
     }
     if (!s->map) {   // from the headers as they are now
-        rc = quiesce(s->v, s->h);
+        rc = pu::resident_quiesce(s->h);
         if (rc) return rc;
     }
     // on the set's own stream, after the last gather by the set's event (and so after whatever the
@@ -547,10 +510,10 @@ int pu_dres_read_queue_totals(pu_dres* s, uint64_t* n_out, uint64_t* n1_out, siz
     const int G = s->last_n < s->groups ? s->last_n : s->groups;
     const unsigned tiles = (unsigned)((nq + kThreads - 1) / kThreads);
     if (s->map)
-        hipLaunchKernelGGL((dres_totals_partial_kernel<true>), dim3(tiles, (unsigned)G), dim3(kThreads), 0, st, s->v.arena,
+        hipLaunchKernelGGL((dres_totals_partial_kernel<true>), dim3(tiles, (unsigned)G), dim3(kThreads), 0, st, s->h->arena,
                            s->g, s->last_first, s->last_n, G, s->map_n, s->map_n1, s->slab_n, s->slab_n1);
     else
-        hipLaunchKernelGGL((dres_totals_partial_kernel<false>), dim3(tiles, (unsigned)G), dim3(kThreads), 0, st, s->v.arena,
+        hipLaunchKernelGGL((dres_totals_partial_kernel<false>), dim3(tiles, (unsigned)G), dim3(kThreads), 0, st, s->h->arena,
                            s->g, s->last_first, s->last_n, G, (const uint64_t*)nullptr, (const uint64_t*)nullptr, s->slab_n,
                            s->slab_n1);
     hipLaunchKernelGGL(dres_totals_sum_kernel, dim3(tiles), dim3(kThreads), 0, st, s->slab_n, s->slab_n1, G, nq, s->tot_n,
@@ -565,23 +528,22 @@ int pu_dres_read_queue_totals(pu_dres* s, uint64_t* n_out, uint64_t* n1_out, siz
         "reading the per-queue totals failed");
 }
 
-int pu_num_links(const pu_handle* h) { return h ? pu::handle_view(const_cast<pu_handle*>(h)).geo->nlinks : 0; }
-int pu_num_queues(const pu_handle* h) { return h ? pu::handle_view(const_cast<pu_handle*>(h)).geo->nqueues : 0; }
+int pu_num_links(const pu_handle* h) { return h ? h->geo.nlinks : 0; }
+int pu_num_queues(const pu_handle* h) { return h ? h->geo.nqueues : 0; }
 int pu_dres_nqueues(const pu_dres* s) { return s ? s->g.nqueues : 0; }
 uint64_t pu_dres_state_bytes(const pu_dres* s) { return s ? (uint64_t)s->bytes : 0; }
 
 int pu_dres_host_gather(pu_handle* h, int replica, pu_dres_replica* out, uint64_t* n_out, uint64_t* n1_out, size_t cap) {
     if (!h || !out) return pu::set_error(PU_EINVAL, "pu_dres_host_gather: bad arguments");
-    const pu::HandleView v = pu::handle_view(h);
-    const Geo& g = *v.geo;
-    if (replica < 0 || replica >= v.R) return pu::set_error(PU_ERANGE, "replica out of range");
+    const Geo& g = h->geo;
+    if (replica < 0 || replica >= h->R) return pu::set_error(PU_ERANGE, "replica out of range");
     const size_t nq = (size_t)g.nqueues, nc = (size_t)g.num_cores;
     if ((n_out || n1_out) && cap < nq)
         return pu::set_error(PU_ERANGE, "pu_dres_host_gather: room for fewer queues than a replica has");
     std::memset(out, 0, sizeof *out);
     int rc = pu_stats_get(h, replica, &out->stats);   // joins a resident kernel and waits for the handle's stream
     if (rc) return rc;
-    const char* const base = v.arena + (size_t)replica * g.replica_bytes;
+    const char* const base = h->arena + (size_t)replica * g.replica_bytes;
     std::vector<int64_t> cyc(nc);
     std::vector<uint32_t> hdr(nq * (kHdrBytes / 4));
     RunState run;
@@ -620,56 +582,6 @@ int pu_dres_host_gather(pu_handle* h, int replica, pu_dres_replica* out, uint64_
     out->link_max_id = lm.id;
     out->bus_max_visits = bm.visits;
     out->bus_max_id = bm.id;
-    return 0;
-}
-
-// The engine's record numbering (engine.hip:1023-1047, net_route_link), inverted.
-int pu_config_queue_ends(const pu_sim_cfg* cfg, int q, int* kind, int* a, int* b) {
-    if (!cfg || !kind || !a || !b) return pu::set_error(PU_EINVAL, "pu_config_queue_ends: bad arguments");
-    Geo g;
-    int rc = pu::config_geometry(cfg, &g);
-    if (rc) return rc;
-    *kind = *a = *b = -1;
-    if (q < 0 || q >= g.nqueues) return 0;
-    if (q >= g.nlinks) {
-        for (int l = 0; l < g.num_levels; l++) {
-            const LevelGeo& L = g.lv[l];
-            if (L.has_bus && q >= L.bus_q0 && q < L.bus_q0 + L.ncaches) {
-                *kind = 3;
-                *a = l;
-                *b = q - L.bus_q0;
-            }
-        }
-        return 0;
-    }
-    const int w = g.net_width, w1 = w - 1;   // nlinks > 0, so w > 1
-    const int row = q / w1, low = q % w1;    // the record's row of w - 1 edges; the lower coordinate along it
-    if (g.net_type != 1) {
-        if (row < w) {          // x: row = y
-            *kind = 0;
-            *a = row * w + low;
-            *b = *a + 1;
-        } else {                // y: row = w + x
-            *kind = 1;
-            *a = low * w + (row - w);
-            *b = *a + w;
-        }
-        return 0;
-    }
-    const int w2 = w * w, blk = row / w2, rr = row % w2, hi = rr / w, lo = rr % w;
-    if (blk == 0) {             // x: row = z*w + y
-        *kind = 0;
-        *a = hi * w2 + lo * w + low;
-        *b = *a + 1;
-    } else if (blk == 1) {      // y: row = z*w + x
-        *kind = 1;
-        *a = hi * w2 + low * w + lo;
-        *b = *a + w;
-    } else {                    // z: row = y*w + x
-        *kind = 2;
-        *a = low * w2 + hi * w + lo;
-        *b = *a + w2;
-    }
     return 0;
 }
 

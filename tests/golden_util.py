@@ -16,7 +16,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 def _all_names() -> list[str]:
     return sorted(f[:-5] for f in os.listdir(GOLDEN) if f.endswith(".json") and f not in
-                  ("network.json", "configs.json"))
+                  ("network.json", "configs.json", "geo_source.json"))
 
 
 def case_names() -> list[str]:

@@ -9,8 +9,8 @@ The engine has six compiled kernels per configuration (jit.cpp):
     pu_jit_uncore_s2_h0   pu_run_device_pool (the benchmark's headline kernel)
     pu_jit_uncore_s3_h1   the resident mailbox kernel
 
-Which one a call gets is decided in uncore.cpp (launch, resident_eligible,
-access_batch).  `run_cell` drives a golden through the calls that reach one of
+Which one a call gets is decided in uncore.cpp (launch, access_batch) and
+resident.cpp (resident_eligible).  `run_cell` drives a golden through the calls that reach one of
 them, checks after every launch that pu_last_launch_kernel names that kernel
 (a cell that ran another kernel fails), and checks the results against the
 fixture with equality: every delay, completion cycle, counter, error flag, the
@@ -48,7 +48,7 @@ EXCLUDED = {
     ("mesh_8192", S3_H1): _M8,
 }
 
-RESIDENT_CAP = 16384      # requests per resident command (uncore.cpp kResCap)
+RESIDENT_CAP = 16384      # requests per resident command (resident.cpp kResCap)
 REPLICAS = 3              # the device-path cells: replicas 0 and 2 the golden, replica 1 its second half
 POOL_SLOTS = 2            # ... on two wavefronts in the pool: one takes the third replica mid-slice
 

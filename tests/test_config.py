@@ -1,11 +1,13 @@
 """config_prime XML schema loader vs the reference's XmlParser (xml_parser.cpp)."""
 import ctypes as C
+import hashlib
 import json
 import os
 
 import pytest
 
 import primesim_amd as P
+from abi_helpers import run_cpp_check
 from primesim_amd import _abi as A
 from primesim_amd import config as CF
 from golden_util import GOLDEN, case_names
@@ -95,6 +97,39 @@ def test_write_xml_round_trip():
     assert P.uncore.lib().pu_config_write_xml(C.byref(cfg), buf, len(buf), C.byref(n)) == 0
     again = P.parse_config(buf.value.decode())
     assert _as_dict(again) == _as_dict(cfg)
+
+
+def _geo_source_sha(cfg) -> str:
+    n = P.uncore.lib().pu_config_geo_source(C.byref(cfg), None, 0)
+    assert n > 0, P.uncore.last_error()
+    buf = C.create_string_buffer(n + 1)
+    assert P.uncore.lib().pu_config_geo_source(C.byref(cfg), buf, n + 1) == n
+    return hashlib.sha256(buf.value).hexdigest()
+
+
+def test_geometry_of_every_known_configuration_is_the_recorded_one(monkeypatch):
+    """tests/golden/geo_source.json holds, for every XML under tests/golden and the
+    presets C1-C5, the sha256 of pu_config_geo_source's text as the commit under
+    "_from" produced it.  Every offset, count and flag of a Geo is in that text, so
+    the validation and the replica layout (geometry.cpp) are pinned field by field."""
+    for k in ("PRIMEUNCORE_POOL_ENTRIES", "PRIMEUNCORE_PAGE_ENTRIES"):   # both size a part of the layout
+        monkeypatch.delenv(k, raising=False)
+    with open(os.path.join(GOLDEN, "geo_source.json")) as f:
+        want = json.load(f)
+    assert len(want.pop("_from")) == 40
+    xmls = sorted(os.path.splitext(n)[0] for n in os.listdir(GOLDEN) if n.endswith(".xml"))
+    presets = ["C1", "C2", "C3", "C4", "C5"]
+    assert sorted(want) == sorted(xmls + [f"preset:{p}" for p in presets])
+    got = {name: _geo_source_sha(P.load_config(os.path.join(GOLDEN, f"{name}.xml"))) for name in xmls}
+    got.update({f"preset:{p}": _geo_source_sha(P.config_from_dict(CF.preset(p))) for p in presets})
+    assert {k: v for k, v in got.items() if v != want[k]} == {}
+
+
+def test_host_geometry_under_the_sanitizers(tmp_path):
+    """common.cpp, config.cpp and geometry.cpp need no HIP: tests/cpp/geometry_check.cpp
+    runs them under the address and undefined-behaviour sanitizers (144 links of the
+    3D mesh, 16 buses of the bus system, 24 links of the TLB configuration)."""
+    assert run_cpp_check(tmp_path, "geometry_check.cpp").startswith("OK 184 queues")
 
 
 def test_dram_bank_element_round_trip():

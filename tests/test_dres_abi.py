@@ -162,3 +162,9 @@ def test_header_decode_fold_and_tie_rule_equal_literal_arithmetic(tmp_path):
     """7 edge counts x 128 cursor values + 100,000 random pairs; the completion fold and the
     busiest-queue rule against sequential loops."""
     assert run_cpp_check(tmp_path, "queue_header_check.cpp").startswith("OK 100896 headers")
+
+
+def test_the_stats_rule_writes_every_field_from_its_source(tmp_path):
+    """pu::stats_fill (stats_rule.h), the one rule pu_stats_get and the device gather share: 45 fields
+    against their literals for 1 and for 4 levels, on a record pre-filled with 0xA5."""
+    assert run_cpp_check(tmp_path, "stats_rule_check.cpp").startswith("OK 90 fields")
