@@ -64,6 +64,10 @@ int pu::config_geometry(const pu_sim_cfg* c, Geo* g, uint64_t pool_cap) {
         L.nchildren = l == 0 ? 0 : cc.share / y.cache[l - 1].share;
         L.has_bus = cc.share > 1 ? 1 : 0;
         if (l > 0 && cc.share % y.cache[l - 1].share != 0) return pu::set_error(PU_EINVAL, "cache shares must nest");
+        if (l > 0 && g->lv[l - 1].ncaches % L.nchildren != 0)
+            return pu::set_error(PU_ENOTSUP, "a shared level's children must fill every parent (num_caches is a ceil, "
+                                             "system.cpp:76; init_caches gives the last parent all share ratio "
+                                             "children, system.cpp:184-188)");
         if (L.has_bus) {
             if (y.bus_latency < 1) return pu::set_error(PU_EINVAL, "bus_latency must be >= 1 for shared levels");
             L.bus_q0 = nbus;   // fixed up below (after the link count is known)
@@ -94,6 +98,11 @@ int pu::config_geometry(const pu_sim_cfg* c, Geo* g, uint64_t pool_cap) {
         return pu::set_error(PU_EINVAL, "limited-pointer broadcast needs one LLC per core (system.cpp:623)");
     if (!bus_sys && y.network.link_delay < 1) return pu::set_error(PU_EINVAL, "link_delay must be >= 1");
     if (y.network.data_width < 1) return pu::set_error(PU_EINVAL, "data_width must be >= 1");
+    if (y.network.header_flits < 1)
+        return pu::set_error(PU_ENOTSUP, "header_flits must be >= 1 (a zero-flit packet, network.cpp:104: touching "
+                                         "intervals make the tree search depend on the tree's shape, "
+                                         "queue_model_history_tree.cpp:66; a zero service rate, "
+                                         "queue_model_m_g_1.cpp:28-35)");
     if (y.network.router_delay >= (1ull << 31) || y.network.link_delay >= (1ull << 31) ||
         y.network.inject_delay >= (1ull << 31))
         return pu::set_error(PU_ENOTSUP, "router/link/inject delays must be < 2^31 cycles");

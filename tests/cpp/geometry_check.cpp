@@ -5,9 +5,11 @@
 // pu_config_parse_xml, pu::config_geometry and pu::geo_cxx; then
 // pu_config_queue_ends is asked about every q in [-1, nqueues] and the ends must
 // round-trip (a link's b - a is 1, w or w * w by its kind; a bus id lies in its
-// level's range).  Two configurations the validation refuses must fail with
-// their texts.  Host only (tests/test_config.py builds it with the host's
-// address and undefined-behaviour sanitizers).
+// level's range).  Configurations the validation refuses must fail with their
+// texts: no levels, too many ways, zero-flit packets, and a shared level whose
+// children do not fill its last parent (next to ones that do, which pass).
+// Host only (tests/test_config.py builds it with the host's address and
+// undefined-behaviour sanitizers).
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -281,6 +283,43 @@ int main() {
     bad = cfg;
     bad.sys.cache[0].num_ways = 4097;
     if (!refused("4097 ways", bad, PU_ENOTSUP, "at most 4096 ways per set")) return 1;
+
+    // zero-flit packets (network.cpp:104), whatever the system
+    static const char k_flits[] =
+        "header_flits must be >= 1 (a zero-flit packet, network.cpp:104: touching intervals make the tree search "
+        "depend on the tree's shape, queue_model_history_tree.cpp:66; a zero service rate, "
+        "queue_model_m_g_1.cpp:28-35)";
+    bad = cfg;
+    bad.sys.network.header_flits = 0;
+    if (!refused("header_flits 0", bad, PU_ENOTSUP, k_flits)) return 1;
+    bad.sys.network.header_flits = -1;
+    if (!refused("header_flits -1", bad, PU_ENOTSUP, k_flits)) return 1;
+    bad.sys.network.header_flits = 1;
+    Geo g;
+    if (pu::config_geometry(&bad, &g) != 0 || g.header_flits != 1) return !fail("header_flits 1", pu_last_error());
+
+    // a shared level whose children do not fill its last parent (system.cpp:76, :184-188)
+    static const char k_fill[] =
+        "a shared level's children must fill every parent (num_caches is a ceil, system.cpp:76; init_caches gives "
+        "the last parent all share ratio children, system.cpp:184-188)";
+    pu_sim_cfg l2;
+    std::memset(&l2, 0, sizeof l2);
+    if (pu_config_parse_xml(k_bus_l2_shared, sizeof k_bus_l2_shared - 1, &l2) != 0) return 1;
+    static const struct { int cores, share; bool ok; } fills[] = {
+        {9, 2, false}, {2, 8, false}, {10, 4, false}, {12, 4, true}, {64, 4, true}};
+    for (const auto& f : fills)
+        for (int sys_type = 0; sys_type < 2; sys_type++) {
+            bad = l2;
+            bad.sys.sys_type = sys_type;
+            bad.sys.num_cores = f.cores;
+            bad.sys.cache[1].share = f.share;
+            const std::string name = std::to_string(f.cores) + " cores, share " + std::to_string(f.share);
+            if (!f.ok) {
+                if (!refused(name.c_str(), bad, PU_ENOTSUP, k_fill)) return 1;
+            } else if (pu::config_geometry(&bad, &g) != 0 || g.lv[1].ncaches * f.share != f.cores) {
+                return !fail(name.c_str(), pu_last_error());
+            }
+        }
 
     std::printf("OK %ld queues\n", total);
     return 0;

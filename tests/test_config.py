@@ -125,10 +125,77 @@ def test_geometry_of_every_known_configuration_is_the_recorded_one(monkeypatch):
     assert {k: v for k, v in got.items() if v != want[k]} == {}
 
 
+PU_ENOTSUP = -95   # include/primeuncore.h
+
+
+def _geometry_rc(sim) -> tuple:
+    """pu::config_geometry's code and text for a configuration (pu_config_queue_ends returns both as they are)."""
+    cfg = P.config_from_dict(sim)
+    kind, a, b = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = P.uncore.lib().pu_config_queue_ends(C.byref(cfg), 0, C.byref(kind), C.byref(a), C.byref(b))
+    return rc, (P.uncore.last_error() if rc else "")
+
+
+def _shared_l2(cores: int, share: int) -> dict:
+    sim = CF.preset("C1")
+    s = sim["system"]
+    s["num_cores"] = cores
+    s["num_levels"] = 2
+    s["cache"] = [
+        {"level": 0, "share": 1, "access_time": 1, "size": 8192, "block_size": 64, "num_ways": 4},
+        {"level": 1, "share": share, "access_time": 6, "size": 65536, "block_size": 64, "num_ways": 8},
+    ]
+    return sim
+
+
+@pytest.mark.parametrize("cores,share,ok", [(9, 2, False), (2, 8, False), (10, 4, False), (12, 4, True),
+                                            (64, 4, True)])
+def test_a_level_whose_children_do_not_fill_the_last_parent_is_refused(cores, share, ok):
+    """The reference counts a level's caches with a ceil (system.cpp:76) but gives
+    every parent share[l] / share[l-1] children (system.cpp:184-188): the last
+    parent of an unfilled level reads child pointers past its level's array."""
+    rc, text = _geometry_rc(_shared_l2(cores, share))
+    if ok:
+        assert rc == 0, text
+    else:
+        assert rc == PU_ENOTSUP and "system.cpp:184-188" in text and "system.cpp:76" in text
+        with pytest.raises(P.UncoreError, match="fill every parent"):    # refused before any device is touched
+            P.UncoreManager().init(P.config_from_dict(_shared_l2(cores, share)))
+
+
+def test_unfilled_parents_are_refused_at_every_level():
+    sim = _shared_l2(12, 2)      # 12 L1, 6 L2; an L3 of share 8 takes 4 L2 each: 6 % 4 != 0
+    sim["system"]["num_levels"] = 3
+    sim["system"]["cache"].append({"level": 2, "share": 8, "access_time": 9, "size": 131072, "block_size": 64,
+                                   "num_ways": 8})
+    assert _geometry_rc(sim)[0] == PU_ENOTSUP
+    sim["system"]["num_cores"] = 16
+    assert _geometry_rc(sim) == (0, "")
+
+
+@pytest.mark.parametrize("sys_type", [0, 1])
+def test_zero_flit_packets_are_refused(sys_type):
+    """header_flits = 0 makes a message without data a packet of no flits
+    (network.cpp:104).  The reference's free intervals then touch, so which of
+    two its tree search returns depends on the tree's shape
+    (queue_model_history_tree.cpp:66), and a link that has carried only such
+    packets has a service rate of 1/0, whose waiting time is a NaN cast to an
+    integer (queue_model_m_g_1.cpp:28-35): neither is restated."""
+    for hf, want in ((0, PU_ENOTSUP), (-1, PU_ENOTSUP), (1, 0)):
+        sim = CF.preset("C1", header_flits=hf, sys_type=sys_type)
+        rc, text = _geometry_rc(sim)
+        assert rc == want, text
+        if want:
+            assert "header_flits must be >= 1" in text and "network.cpp:104" in text
+            with pytest.raises(P.UncoreError, match="header_flits"):
+                P.UncoreManager().init(P.config_from_dict(sim))
+
+
 def test_host_geometry_under_the_sanitizers(tmp_path):
     """common.cpp, config.cpp and geometry.cpp need no HIP: tests/cpp/geometry_check.cpp
     runs them under the address and undefined-behaviour sanitizers (144 links of the
-    3D mesh, 16 buses of the bus system, 24 links of the TLB configuration)."""
+    3D mesh, 16 buses of the bus system, 24 links of the TLB configuration; the
+    refusals of unfilled parents and of zero-flit packets)."""
     assert run_cpp_check(tmp_path, "geometry_check.cpp").startswith("OK 184 queues")
 
 

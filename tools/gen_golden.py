@@ -64,6 +64,31 @@ def _l2_shared(cores: int) -> dict:
     return sim
 
 
+def _four_level(cores: int) -> dict:
+    sim = _three_level(cores)
+    s = sim["system"]
+    s["num_levels"] = 4
+    s["cache"] = [
+        {"level": 0, "share": 1, "access_time": 1, "size": 4096, "block_size": 64, "num_ways": 2},
+        {"level": 1, "share": 2, "access_time": 3, "size": 16384, "block_size": 64, "num_ways": 4},
+        {"level": 2, "share": 4, "access_time": 6, "size": 65536, "block_size": 64, "num_ways": 8},
+        {"level": 3, "share": 16, "access_time": 12, "size": 262144, "block_size": 64, "num_ways": 16},
+    ]
+    return sim
+
+
+def _with_block(sim: dict, block: int) -> dict:
+    for c in sim["system"]["cache"]:
+        c["block_size"] = block
+    sim["system"]["directory_cache"]["block_size"] = block
+    return sim
+
+
+def _with_sys(sim: dict, **kw) -> dict:
+    sim["system"].update(kw)
+    return sim
+
+
 def cases() -> dict:
     S = P.StreamSpec
     c = {}
@@ -165,6 +190,41 @@ def cases() -> dict:
                                          max_requests=20000), {"replay": "closed"})
     c["c4_closed"] = (CF.preset("C4"), S(A.PU_STREAM_UNIFORM_HOTSPOT, 1024, seed=34, quantum=40, num_quanta=2,
                                          max_requests=30000), {"replay": "closed"})
+    # ---- the configuration axes no fixture above varies (each at the smallest
+    # stream that still evicts, broadcasts and laps a queue ring)
+    HOT, SHU, MP = A.PU_STREAM_UNIFORM_HOTSPOT, A.PU_STREAM_SHARED_UNIFORM, A.PU_STREAM_MULTIPROGRAM
+    closed = {"replay": "closed"}
+    # block sizes other than 64 (offbits, home_offbits, plen_blk = 3 + ceil(block / 10))
+    c["blk32"] = (_with_block(_c1_shape(16), 32), S(HOT, 16, seed=201, num_quanta=2))
+    c["blk128"] = (_with_block(_c1_shape(16), 128), S(SHU, 16, seed=202, num_quanta=2))
+    c["blk128_three_level"] = (_with_block(_three_level(64), 128),
+                               S(SHU, 64, seed=203, num_quanta=1, max_requests=12000))
+    # num_levels = 4 (PU_MAX_LEVELS): shares 1, 2, 4, 16, three levels of buses
+    c["four_level"] = (_four_level(64), S(SHU, 64, seed=205, num_quanta=1, max_requests=12000))
+    c["bus_four_level"] = (_with_sys(_four_level(64), sys_type=1),
+                           S(MP, 64, seed=206, num_quanta=1, num_progs=2, max_requests=12000))
+    # closed-loop replay of the systems it never met: bus, TLB, limited pointer,
+    # directory-only on a 3-D mesh, three levels
+    c["bus_closed"] = (_c1_shape(16, sys_type=1), S(HOT, 16, seed=207, num_quanta=3), closed)
+    c["tlb_closed"] = (_c1_shape(16, tlb_enable=1), S(MP, 16, seed=208, num_quanta=3, num_progs=2), closed)
+    c["limited_ptr1_closed"] = (_c1_shape(16, protocol_type=1, max_num_sharers=1),
+                                S(HOT, 16, seed=209, num_quanta=3), closed)
+    # limited pointer over two bitmap words (10 x 10 mesh)
+    c["limited_ptr_100"] = (_c1_shape(100, protocol_type=1, max_num_sharers=4),
+                            S(HOT, 100, seed=210, quantum=50, num_quanta=2, max_requests=12000))
+    c["dironly_3d_closed"] = (_c1_shape(27, shared_llc=0, net_type=1, router_delay=2),
+                              S(A.PU_STREAM_PRODUCER_CONSUMER, 27, seed=211, num_quanta=3, max_requests=12000),
+                              closed)
+    c["three_level_closed"] = (_three_level(64), S(SHU, 64, seed=212, num_quanta=1, max_requests=12000), closed)
+    # mesh widths 3 and 12 (the magic divisions of pu_set_net_magic); 65-flit blocks
+    c["mesh_9_narrow"] = (_c1_shape(9, data_width=1), S(HOT, 9, seed=213, num_quanta=2))
+    # 130 nodes on a 12 x 12 mesh (the last row has holes), three bitmap words
+    c["mesh_130"] = (_c1_shape(130), S(HOT, 130, seed=214, quantum=30, num_quanta=2, max_requests=12000))
+    # write shares other than the generators' own
+    c["writes_90"] = (CF.preset("C1"), S(SHU, 16, seed=216, num_quanta=2, write_pct=90))
+    c["writes_0"] = (CF.preset("C1"), S(HOT, 16, seed=217, num_quanta=2, write_pct=0))
+    # N = 1: a mesh of width 1 has no link and no queue
+    c["one_core"] = (_c1_shape(1), S(A.PU_STREAM_PRIVATE_STREAMING, 1, seed=218, num_quanta=3))
     # full-size runs at the presets, stored as digests (requests regenerate from
     # the stream spec; delays by sha256, completion cycles and report in full)
     c["big_c4_quantum"] = (CF.preset("C4"), S(A.PU_STREAM_UNIFORM_HOTSPOT, 1024, seed=4, num_quanta=1),
