@@ -22,6 +22,12 @@
 #ifndef PRIMEUNCORE_H
 #define PRIMEUNCORE_H
 
+/* What the host shares with the device engine: the PU_E* codes, PU_RD / PU_WR /
+ * PU_WB, pu_dram_cfg, pu_req, pu_req16 with PU_REQ16_* and PU_REQ_FMT_*, and
+ * the PU_ERRF_* bits.  The engine kernels are compiled against that header
+ * alone; this one is the host API. */
+#include "primeuncore_records.h"
+
 #include <stddef.h>
 #include <stdint.h>
 
@@ -30,21 +36,6 @@ extern "C" {
 #endif
 
 #define PU_MAX_LEVELS 4
-
-/* error codes */
-#define PU_OK          0
-#define PU_EINVAL    (-22)
-#define PU_ENOMEM    (-12)
-#define PU_ENODEV    (-19)
-#define PU_ERANGE    (-34)
-#define PU_EIO        (-5)
-#define PU_ENOTSUP   (-95)
-#define PU_ESTATE    (-71)   /* engine hit a state the reference treats as UB */
-
-/* memory request types — reference src/common.h:61-66 (MemType) */
-#define PU_RD 0
-#define PU_WR 1
-#define PU_WB 2
 
 /* ------------------------------------------------------------------------
  * Configuration: plain-C mirror of the reference's XmlSim/XmlSys/XmlCache/
@@ -71,25 +62,8 @@ typedef struct pu_net_cfg {            /* XmlNetwork, xml_parser.h:57-65 */
     uint64_t inject_delay;
 } pu_net_cfg;
 
-/* DRAM bank timing (north_star stage 4).  Opt-in, no reference counterpart:
- * the reference's Dram is a fixed latency plus a counter (dram.cpp:43-47), and
- * banks = 0 (the default; a config without a <dram> element) is exactly that.
- * With banks > 0 every Dram::access call site of System (system.cpp) becomes
- * an access to one bank of an open-page DRAM at that call's cycle t:
- *   row r = addr >> log2(row_bytes);  bank = r & (banks-1);  page = r >> log2(banks)
- *   start = max(t, bank.ready)
- *   act   = 0 (page open: row hit) | t_rcd (bank closed) | t_rp + t_rcd (other page open)
- *   delay = (start - t) + act + dram_access_time
- *   bank.ready = start + act + t_burst;  bank.open = page
- * Call sites whose Dram::access delay the reference discards (write-backs)
- * still occupy the bank.  banks and row_bytes are powers of two. */
-typedef struct pu_dram_cfg {
-    int32_t  banks;          /* 0 = fixed latency (the reference) */
-    int32_t  t_rcd;          /* activate to column command, cycles */
-    int32_t  t_rp;           /* precharge, cycles */
-    int32_t  t_burst;        /* cycles a bank stays busy after the column command */
-    uint64_t row_bytes;      /* bytes of one row (page) of one bank, >= 64 */
-} pu_dram_cfg;
+/* pu_dram_cfg, the opt-in DRAM bank model and its timing rule:
+ * primeuncore_records.h. */
 
 typedef struct pu_sys_cfg {            /* XmlSys, xml_parser.h:69-89 */
     int32_t  sys_type;                 /* 0 directory, 1 bus */
@@ -141,27 +115,12 @@ int pu_config_write_xml(const pu_sim_cfg* cfg, char* buf, size_t cap, size_t* wr
  * batch_start = 1 marks the first request of a MEM_REQUESTS message: the
  * running-delay rule of prime.cpp:129 restarts there:
  *     D = 0 at batch start;  d_i = access(core, req_i, timer_i + D);  D += d_i - 1
- * ---------------------------------------------------------------------- */
-typedef struct pu_req {
-    uint64_t addr;         /* MsgMem.addr_dmem */
-    int64_t  timer;        /* MsgMem.timer (core cycle when issued) */
-    int32_t  core;         /* core id */
-    int32_t  prog_id;      /* program (Pin process rank, >= 1) */
-    uint8_t  mem_type;     /* PU_RD / PU_WR */
-    uint8_t  batch_start;  /* 1 = first request of a message */
-    uint16_t tag;          /* MPI tag of its message = receive-thread id (prime.cpp:53);
-                              only the server's per-thread stop reads it, 0 elsewhere */
-    int32_t  _pad1;
-} pu_req;                  /* 32 bytes */
-
-/* Compact 16-byte device request record for throughput runs whose requests
- * fit (no reference counterpart: a layout of the same MsgMem fields).
- *   a = addr_dmem
- *   b = timer (bits 0-39) | core (40-55) | prog_id (56-61) | mem_type (62)
- *       | batch_start (63);  tag is 0.
- * The PU_REQ16_* constants below are that layout: PU_REQ16_B packs b from
- * fields that fit and PU_REQ16_TIMER / _CORE / _PROG / _TYPE / _BATCH take
- * them out again.  Every packer and reader of the library goes through them.
+ * The record itself (32 bytes): primeuncore_records.h.
+ *
+ * pu_req16 (there too) is the compact 16-byte device request record for
+ * throughput runs whose requests fit; no reference counterpart.  The
+ * PU_REQ16_* constants are its layout, and every packer and reader of the
+ * library goes through them.
  * pu_pack_req16 packs n records and returns 0, or PU_ERANGE (out untouched
  * past the record it names in the error text) at the first that does not
  * fit: timer outside [0, 2^40), core outside [0, 2^16), prog_id outside
@@ -171,30 +130,8 @@ typedef struct pu_req {
  * records (indices in d_off / d_pos count records either way); those runs
  * use the throughput kernels (a latency launch's helper reads pu_req).
  * Results are identical to the same requests as pu_req.  PU_REQ_FMT_32
- * (the default) restores pu_req.  The host batch paths always take pu_req. */
-typedef struct pu_req16 {
-    uint64_t a, b;
-} pu_req16;
-#define PU_REQ16_TIMER_BITS 40
-#define PU_REQ16_CORE_SHIFT 40
-#define PU_REQ16_CORE_BITS 16
-#define PU_REQ16_PROG_SHIFT 56
-#define PU_REQ16_PROG_BITS 6
-#define PU_REQ16_TYPE_SHIFT 62
-#define PU_REQ16_BATCH_SHIFT 63
-#define PU_REQ16_B(timer, core, prog_id, mem_type, batch_start)               \
-    ((uint64_t)(timer) | (uint64_t)(uint32_t)(core) << PU_REQ16_CORE_SHIFT |  \
-     (uint64_t)(uint32_t)(prog_id) << PU_REQ16_PROG_SHIFT |                   \
-     (uint64_t)(mem_type) << PU_REQ16_TYPE_SHIFT | (uint64_t)(batch_start) << PU_REQ16_BATCH_SHIFT)
-#define PU_REQ16_TIMER(b) ((int64_t)((uint64_t)(b) & (((uint64_t)1 << PU_REQ16_TIMER_BITS) - 1)))
-#define PU_REQ16_CORE(b) \
-    ((int32_t)(((uint64_t)(b) >> PU_REQ16_CORE_SHIFT) & (((uint64_t)1 << PU_REQ16_CORE_BITS) - 1)))
-#define PU_REQ16_PROG(b) \
-    ((int32_t)(((uint64_t)(b) >> PU_REQ16_PROG_SHIFT) & (((uint64_t)1 << PU_REQ16_PROG_BITS) - 1)))
-#define PU_REQ16_TYPE(b) ((uint8_t)(((uint64_t)(b) >> PU_REQ16_TYPE_SHIFT) & 1u))
-#define PU_REQ16_BATCH(b) ((uint8_t)((uint64_t)(b) >> PU_REQ16_BATCH_SHIFT))
-#define PU_REQ_FMT_32 0
-#define PU_REQ_FMT_16 1
+ * (the default) restores pu_req.  The host batch paths always take pu_req.
+ * ---------------------------------------------------------------------- */
 
 /* ------------------------------------------------------------------------
  * Statistics — every number System::report prints (reference
@@ -238,26 +175,12 @@ typedef struct pu_stats {
     uint64_t dram_bank_wait;        /* cycles spent waiting for a busy bank */
 } pu_stats;
 
-#define PU_ERRF_CORE_RANGE   (1ull << 0)  /* core_id >= num_cores (system.cpp:147) */
-#define PU_ERRF_WB_MISS      (1ull << 1)  /* WB missed at home: NULL deref in ref (Q13) */
-#define PU_ERRF_EMPTY_SHARER (1ull << 2)  /* *sharer_set.begin() on empty set */
-#define PU_ERRF_QUEUE        (1ull << 3)  /* queue-model precondition violated */
-#define PU_ERRF_NEG_DELAY    (1ull << 4)  /* batch delay went negative (prime.cpp:130) */
-#define PU_ERRF_POOL         (1ull << 5)  /* sharer-bitmap pool exhausted (engine limit: the
-                                             pool holds one entry per directory line up to
-                                             2 GiB of bitmaps; PRIMEUNCORE_POOL_ENTRIES) */
-#define PU_ERRF_PAGES        (1ull << 6)  /* page table 3/4 full (engine limit: 2^22 slots,
-                                             raise PRIMEUNCORE_PAGE_ENTRIES) */
-#define PU_ERRF_PROG         (1ull << 7)  /* no longer raised: since 0.2 directory lines
-                                             carry any int prog_id (ids outside [0, 1023)
-                                             escape to a side array) */
-/* The bits that mean the replica stopped where the reference would have
+/* The PU_ERRF_* bits of error_flags: primeuncore_records.h.  PU_ERRF_LIMITS
+ * are the bits that mean the replica stopped where the reference would have
  * continued (an engine limit) or reached a state the reference leaves undefined.
  * Not CORE_RANGE (System::access returns -1 and goes on) nor NEG_DELAY
  * (prime.cpp's own stop).  The host batch paths and the server return /
  * report PU_ESTATE for these. */
-#define PU_ERRF_LIMITS (PU_ERRF_WB_MISS | PU_ERRF_EMPTY_SHARER | PU_ERRF_QUEUE | \
-                        PU_ERRF_POOL | PU_ERRF_PAGES | PU_ERRF_PROG)
 
 /* ------------------------------------------------------------------------
  * Engine lifetime and the hot path.
@@ -303,7 +226,10 @@ int pu_compiled_compiler(const pu_handle* h);
 const char* pu_last_launch_kernel(pu_handle* h);
 /* The 8-hex-digit tag of the engine sources this library compiles: the prefix
  * of every code object it writes to the cache (cache maintenance keeps the
- * code objects whose prefix some library still carries). */
+ * code objects whose prefix some library still carries).  It covers the
+ * engine's own sources only (the engine, its geometry header and
+ * primeuncore_records.h), not this header: an edit here leaves the tag and
+ * every cached code object as they are. */
 const char* pu_jit_source_tag(void);
 
 /* Diagnostics, no reference counterpart (tools/prof_regions.py): the

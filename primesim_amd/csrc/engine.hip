@@ -32,9 +32,9 @@
 #endif
 
 #if defined(__HIPCC_RTC__) || defined(PU_JIT_OFFLINE)
-#include "primeuncore.h"      // the same file, registered (hipRTC) or written (offline) under this name by jit.cpp
+#include "primeuncore_records.h"   // the same file, registered (hipRTC) or written (offline) under this name by jit.cpp
 #else
-#include "../../include/primeuncore.h"
+#include "../../include/primeuncore_records.h"
 #endif
 #include "geometry.h"
 

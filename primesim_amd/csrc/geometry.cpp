@@ -246,7 +246,7 @@ long pu_config_geo_source(const pu_sim_cfg* cfg, char* buf, size_t cap) {
     return (long)s.size();
 }
 
-// The engine's record numbering (engine.hip:1023-1047, net_route_link), inverted.
+// The engine's record numbering (engine.hip net_route_link), inverted.
 int pu_config_queue_ends(const pu_sim_cfg* cfg, int q, int* kind, int* a, int* b) {
     if (!cfg || !kind || !a || !b) return pu::set_error(PU_EINVAL, "pu_config_queue_ends: bad arguments");
     Geo g;

@@ -81,6 +81,21 @@ uint64_t fnv1a(const std::string& s, uint64_t h = 1469598103934665603ull) {
     return h;
 }
 
+// The embedded sources (the Makefile's JIT_SRCS, in its order) folded into h:
+// each one's name, then its text.  The source tag and every code object's key
+// hash them through here.
+uint64_t hash_sources(uint64_t h) {
+    for (int i = 0; i < pu_jit_nsrc; i++) {
+        h = fnv1a(pu_jit_src_name[i], h);
+        h = fnv1a(pu_jit_src_text[i], h);
+    }
+    return h;
+}
+
+// The main source among them: the file the compilers are given; the others
+// are the headers it includes by name.
+constexpr const char* kMainSrc = "engine.hip";
+
 std::string lib_dir() {
     Dl_info info;
     if (dladdr((void*)&fnv1a, &info) && info.dli_fname) {
@@ -168,7 +183,7 @@ int compile(const std::string& geo_src, const std::vector<std::string>& opts, st
     std::vector<const char*> hnames, htexts;
     for (int i = 0; i < pu_jit_nsrc; i++) {
         const std::string n = pu_jit_src_name[i];
-        if (n == "engine.hip") main_src = pu_jit_src_text[i];
+        if (n == kMainSrc) main_src = pu_jit_src_text[i];
         else {
             hnames.push_back(pu_jit_src_name[i]);
             htexts.push_back(pu_jit_src_text[i]);
@@ -181,7 +196,7 @@ int compile(const std::string& geo_src, const std::vector<std::string>& opts, st
     hnames.push_back("stddef.h");
     htexts.push_back(kStddef);
     hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, main_src.c_str(), "engine.hip", (int)hnames.size(), htexts.data(),
+    if (hiprtcCreateProgram(&prog, main_src.c_str(), kMainSrc, (int)hnames.size(), htexts.data(),
                             hnames.data()) != HIPRTC_SUCCESS) {
         *log = "hiprtcCreateProgram failed";
         return -1;
@@ -287,7 +302,7 @@ int compile_offline(const std::string& cc, const std::string& geo_src, const std
     for (int i = 0; i < pu_jit_nsrc; i++)
         ok = ok && put(pu_jit_src_name[i], pu_jit_src_text[i], std::strlen(pu_jit_src_text[i]));
     ok = ok && put("pu_jit_geo.h", geo_src.data(), geo_src.size());
-    const std::string out = d + "/out.hsaco", logf = d + "/cc.log", src = d + "/engine.hip";
+    const std::string out = d + "/out.hsaco", logf = d + "/cc.log", src = d + "/" + kMainSrc;
     files.push_back(out);
     files.push_back(logf);
     int rc = -1;
@@ -334,11 +349,7 @@ constexpr const char* kBuildArch = "gfx950";   // the library's own target (Make
 // every code object name it writes (tools/jit_warm.py keeps the code objects
 // whose prefix a library in the tree carries).
 std::string jit_source_tag() {
-    uint64_t h = fnv1a("primeuncore-jit-src");
-    for (int i = 0; i < pu_jit_nsrc; i++) {
-        h = fnv1a(pu_jit_src_name[i], h);
-        h = fnv1a(pu_jit_src_text[i], h);
-    }
+    const uint64_t h = hash_sources(fnv1a("primeuncore-jit-src"));
     char buf[9];
     std::snprintf(buf, sizeof buf, "%08llx", (unsigned long long)(h >> 32));
     return buf;
@@ -357,11 +368,7 @@ const char* jit_kernel_name(int s, int h) {
 }
 
 std::string jit_key(const Geo& g, int waves_1level, const std::string& arch, int part, int cc) {
-    uint64_t h = fnv1a("primeuncore-jit-2");
-    for (int i = 0; i < pu_jit_nsrc; i++) {
-        h = fnv1a(pu_jit_src_name[i], h);
-        h = fnv1a(pu_jit_src_text[i], h);
-    }
+    uint64_t h = hash_sources(fnv1a("primeuncore-jit-2"));
     h = fnv1a(geo_cxx(g), h);
     for (const auto& o : options(arch, waves_1level, part, g.num_levels == 1, cc)) h = fnv1a(o, h);
     int maj = 0, min = 0;
@@ -388,6 +395,15 @@ std::string device_arch() {
     std::string a = p.gcnArchName;
     const size_t k = a.find(':');
     return a.empty() ? std::string(kBuildArch) : a.substr(0, k);
+}
+
+// Where the cache keeps part `part` of configuration g as compiler cc built it.
+struct CacheEntry {
+    std::string key, path;
+};
+CacheEntry cache_entry(const Geo& g, int waves, const std::string& arch, int part, int cc) {
+    const std::string key = jit_key(g, waves, arch, part, cc);
+    return {key, cache_dir() + "/" + key + ".hsaco"};
 }
 
 // Compile configuration g for arch into the cache; 0 or -1 (log filled).
@@ -433,8 +449,7 @@ bool load_part(const Geo& g, int waves, const std::string& arch, int part, JitKe
     std::string log, why;
     // the offline compiler's code object (written at build time: jit_warm), else hipRTC's
     for (int cc : {kJitOffline, kJitRtc}) {
-        const std::string key = jit_key(g, waves, arch, part, cc);
-        const std::string path = cache_dir() + "/" + key + ".hsaco";
+        const auto [key, path] = cache_entry(g, waves, arch, part, cc);
         if (!read_file(path, &code)) continue;
         ::utime(path.c_str(), nullptr);          // in use: tools/jit_warm.py keeps what is used
         if (load_module(code, part, out, &why)) {
@@ -447,8 +462,7 @@ bool load_part(const Geo& g, int waves, const std::string& arch, int part, JitKe
                      why.c_str());
         std::remove(path.c_str());
     }
-    const std::string key = jit_key(g, waves, arch, part, kJitRtc);
-    const std::string path = cache_dir() + "/" + key + ".hsaco";
+    const auto [key, path] = cache_entry(g, waves, arch, part, kJitRtc);
     *key_out = key;
     if (verbose) std::fprintf(stderr, "[primeuncore] compiling the engine for this configuration (%s)\n", key.c_str());
     if (compile_into(g, waves, arch, part, kJitRtc, path, &code, &log) != 0) {
@@ -490,22 +504,21 @@ int jit_warm(const Geo& g, std::string* key_out) {
     std::lock_guard<std::mutex> lk(g_jit_mu);
     int cached = 0;
     for (int part = 0; part < kJitParts; part++) {
-        const std::string ko = jit_key(g, waves, kBuildArch, part, kJitOffline);
-        const std::string kr = jit_key(g, waves, kBuildArch, part, kJitRtc);
-        const std::string po = cache_dir() + "/" + ko + ".hsaco", pr = cache_dir() + "/" + kr + ".hsaco";
+        const CacheEntry eo = cache_entry(g, waves, kBuildArch, part, kJitOffline);
+        const CacheEntry er = cache_entry(g, waves, kBuildArch, part, kJitRtc);
         struct stat st;
-        const bool have_o = ::stat(po.c_str(), &st) == 0 && st.st_size > 0;
-        const bool have_r = !have_o && ::stat(pr.c_str(), &st) == 0 && st.st_size > 0;
-        if (key_out && part == 0) *key_out = have_o || offline ? ko : kr;
+        const bool have_o = ::stat(eo.path.c_str(), &st) == 0 && st.st_size > 0;
+        const bool have_r = !have_o && ::stat(er.path.c_str(), &st) == 0 && st.st_size > 0;
+        if (key_out && part == 0) *key_out = have_o || offline ? eo.key : er.key;
         if (have_o || (have_r && !offline)) {
-            ::utime((have_o ? po : pr).c_str(), nullptr);   // still in use (tools/jit_warm.py prunes what is not)
+            ::utime((have_o ? eo : er).path.c_str(), nullptr);   // still in use (tools/jit_warm.py prunes what is not)
             cached++;
             continue;
         }
         std::vector<char> code;
         std::string log;
         const int cc = offline ? kJitOffline : kJitRtc;
-        if (compile_into(g, waves, kBuildArch, part, cc, cc == kJitOffline ? po : pr, &code, &log) != 0)
+        if (compile_into(g, waves, kBuildArch, part, cc, (offline ? eo : er).path, &code, &log) != 0)
             return set_error(PU_EIO, std::string(cc == kJitOffline ? "hipcc: " : "hipRTC: ") + log);
     }
     return cached == kJitParts ? 1 : 0;

@@ -15,7 +15,7 @@
 
 namespace pu_run_results {
 
-// The engine's packed queue header, restated (engine.hip:803-864; engine.hip is
+// The engine's packed queue header, restated (engine.hip q_store_hdr / hdr_state; engine.hip is
 // embedded for the per-configuration compile and cannot include this file, so
 // tests/test_gpu_dres.py is what pins the two together).  32 B per queue, two
 // 16-B pieces; the first, a = {n | head, n1 | count}, is four dwords:
