@@ -726,6 +726,90 @@ int pu_replica_fork(pu_handle* h, int src, int first, int n, int flags, void* hi
 int pu_stream_fork(pu_stream* dst, const pu_stream* src, int reseed, uint64_t seed);
 int pu_dstream_fork(pu_dstream* s, int src, int first, int n, const uint64_t* seeds, void* hip_stream);
 
+/* One recorded trace replayed across an ensemble, placed per replica on the device (no
+ * reference counterpart; the recorded-trace counterpart of pu_dstream_*: pu_dtrace_next ->
+ * pu_run_device / _sliced / _pool -> pu_dsum_add, with the trace on the device once and no
+ * request staged from the host).  Every replica of a handle shares one configuration, so
+ * replicas of one trace are copies of one answer until something distinguishes them.  Two
+ * things do, both a rewrite of two fields of each record:
+ *   placement  a bijection of the trace's cores onto the configuration's, per replica: the
+ *              thread-placement study of a NoC or a shared cache;
+ *   skew       a constant added to the timers of each core, per replica: a sample of the
+ *              interleavings a multi-threaded run could have taken.
+ * A placement acts on the core ids a recorded trace already holds (pu_msglog_next has
+ * resolved them).  The per-replica thread schedulers (pu_alloc_core_replica) are the other
+ * end: they resolve (program, thread) to a core for the drop-in path, one request at a time.
+ *
+ * The rule (primesim_amd/csrc/trace_place_step.h), for a source record q of a replica with
+ * placement row `place` and skew row `skew` (int32[num_cores] each; NULL = identity / zeros):
+ *   core'  = place[q.core]
+ *   timer' = q.timer + skew[q.core]           (indexed by the trace's core, not the placed one)
+ *   addr, prog_id, mem_type, batch_start and tag are unchanged.
+ * As pu_req (PU_REQ_FMT_32) all 32 bytes are written, _pad1 = 0 and tag copied; as pu_req16
+ * (PU_REQ_FMT_16) the record is pu_pack_req16 of that 32-byte result.
+ *
+ * pu_dtrace_open: a set of `count` replicas over trace[0, n), whose cores lie in
+ * [0, num_cores), with placement and skew as [count][num_cores] arrays (either may be NULL).
+ * The trace is copied to `device` once and shared by all replicas; the rows are copied as
+ * they are (32 B per record, 4 B per core, replica and table given).  Everything is checked
+ * on the host before a device is touched; NULL + pu_last_error() on failure:
+ *   PU_EINVAL  no trace, n == 0, count <= 0, num_cores outside 1 .. 65536;
+ *   PU_ERANGE  a record whose core is outside [0, num_cores), naming the record;
+ *   PU_EINVAL  a placement row that is no permutation of [0, num_cores), naming the replica
+ *              and the first entry that is out of range or repeats an earlier one;
+ *   PU_EINVAL  a negative skew, naming the replica and the core;
+ *   PU_ERANGE  the largest timer plus the largest skew overflows int64;
+ *   then "no HIP device" where there is none, as pu_create, and PU_ENOMEM with the size asked
+ *   for when the device memory cannot be had.
+ * The set fits pu_req16 when the largest timer plus the largest skew is below 2^40, no timer
+ * is negative, every prog_id is in [0, 64), mem_type and batch_start are at most 1 and tag
+ * is 0 (a placed core is below 65536 by construction): what pu_pack_req16 asks of every
+ * placed record, decided once at open from the maxima, so it may refuse a set whose largest
+ * timer and largest skew never meet.  pu_dtrace_fits_req16: 0, or PU_ERANGE with the reason.
+ *
+ * pu_dtrace_next: the contract of pu_dstream_next with one cursor for the whole set:
+ * got = min(n_each, n - position); replica i's records [position, position + got) are placed
+ * by replica i's rows and written to d_out[i*stride .. i*stride + got) (indices in records of
+ * the chosen format; offsets are 64-bit); nothing else is written; d_got (device, count
+ * uint64, may be NULL) receives got for every replica; the position advances by got.
+ * stride >= n_each and d_out 16-byte aligned, else PU_EINVAL; PU_REQ_FMT_16 on a set that
+ * does not fit: PU_ERANGE with the reason, before anything is launched (PU_REQ_FMT_32 still
+ * serves that set).  Asynchronous on hip_stream (NULL = the set's own stream) and ordered
+ * with the set's other calls as for pu_dstream_next.
+ *
+ * pu_dtrace_seek moves the cursor (0 <= position <= n, else PU_ERANGE; seek(0) replays the
+ * trace) and pu_dtrace_position returns it (or PU_E*); both wait only for the set's
+ * outstanding calls, never for the device, for the reason given for pu_dstream_* above.
+ * pu_dtrace_state_bytes: device memory the set holds.  A NULL set: PU_EINVAL, 0, no-op.
+ *
+ * pu_trace_place: the same rule on host arrays, one replica's rows at a time (no device):
+ * out holds n pu_req or n pu_req16 records.  It checks num_cores, the rows and every
+ * record's core as pu_dtrace_open does, a timer plus skew that overflows int64 (PU_ERANGE),
+ * and for PU_REQ_FMT_16 stops with PU_ERANGE at the first placed record that pu_pack_req16
+ * would refuse, naming it (out untouched past it).
+ *
+ * pu_placement_shuffle: a placement row drawn from a seed, the same for every caller: the
+ * identity for seed 0; otherwise the identity shuffled by Fisher-Yates from the top: for
+ * i = num_cores - 1 down to 1, row[i] is swapped with row[j], j = draw mod (i + 1), the draws
+ * being the splitmix64 sequence of the stream generators started at state `seed`
+ * (z = (state += 0x9E3779B97F4A7C15); z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB; draw = z ^ z >> 31).  PU_EINVAL for a NULL row or
+ * num_cores outside 1 .. 65536. */
+typedef struct pu_dtrace pu_dtrace;
+pu_dtrace* pu_dtrace_open(const pu_req* trace, size_t n, int num_cores, int count,
+                          const int32_t* placement /* [count][num_cores] or NULL */,
+                          const int32_t* skew      /* [count][num_cores] or NULL */, int device);
+void     pu_dtrace_close(pu_dtrace* s);
+int      pu_dtrace_next(pu_dtrace* s, void* d_out, size_t n_each, size_t stride, int fmt,
+                        uint64_t* d_got, void* hip_stream);
+int      pu_dtrace_seek(pu_dtrace* s, int64_t position);
+int64_t  pu_dtrace_position(pu_dtrace* s);
+int      pu_dtrace_fits_req16(const pu_dtrace* s);
+uint64_t pu_dtrace_state_bytes(const pu_dtrace* s);
+int pu_trace_place(const pu_req* in, size_t n, const int32_t* place_row, const int32_t* skew_row,
+                   int num_cores, int fmt, void* out);
+int pu_placement_shuffle(int32_t* row, int num_cores, uint64_t seed);
+
 /* Log-linear delay histograms kept on the device (no reference counterpart; a stage beside
  * pu_dsum_add on the same stream: pu_dstream_next -> pu_run_device -> pu_dsum_add ->
  * pu_dhist_add).  The 32 power-of-two buckets of pu_dsum_replica place a quantile within a

@@ -32,6 +32,19 @@ and every other stream continues from stream 0's position with its own seed
 (DeviceStreamSet.fork), all on the same stream, and the --chunks measured chunks run as
 usual.  The forks share their warm-up: they are correlated until their own streams have
 displaced it, and engine counters ("results", error flags) include the warm-up's.
+
+With --msglog PATH (instead of --kind) the requests are one recorded MsgMem message log,
+read once (msglog_read over the configuration's cores) and replayed on the device for every
+replica (DeviceTraceSet.next_into in place of DeviceStreamSet's): --placement-seed S runs
+replica r under row r of random_placements(replicas, cores, S), --skew-max K adds to every
+core of replica r > 0 a start skew drawn from [0, K] (numpy's default_rng([S, r]); S = 0
+without --placement-seed); replica 0 always runs the trace as recorded.  Every line carries
+"placement_seed" (placement_seed(S, r); 0 is the identity) in place of "seed".  --chunks
+chunks of --chunk requests must lie inside the log.  --warmup-chunks runs replica 0 alone on
+the log's first chunks, forks it to the others, and all continue from the same position: the
+cursor is the set's, so there is no stream to fork.
+
+  python tools/ensemble_summary.py --preset C1 --msglog run.msglog --replicas 8 --placement-seed 5
 """
 from __future__ import annotations
 
@@ -138,7 +151,13 @@ def main() -> int:
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--preset", default="C1", help="C1 .. C5 (primesim_amd.config.preset)")
     g.add_argument("--xml", help="a config_prime XML file instead of a preset")
-    ap.add_argument("--kind", type=int, default=4, help="PU_STREAM_* kind of the synthetic streams (1 .. 6)")
+    src = ap.add_mutually_exclusive_group()
+    src.add_argument("--kind", type=int, default=4, help="PU_STREAM_* kind of the synthetic streams (1 .. 6)")
+    src.add_argument("--msglog", help="a recorded MsgMem message log to replay instead of synthetic streams")
+    ap.add_argument("--placement-seed", type=int, default=None,
+                    help="with --msglog: replica r runs under row r of random_placements(replicas, cores, seed)")
+    ap.add_argument("--skew-max", type=int, default=0,
+                    help="with --msglog: per-core start skew of replicas 1 .., drawn from [0, skew-max]")
     ap.add_argument("--replicas", type=int, default=4)
     ap.add_argument("--chunk", type=int, default=2000, help="requests per replica and chunk")
     ap.add_argument("--chunks", type=int, default=2)
@@ -150,7 +169,10 @@ def main() -> int:
     ap.add_argument("--warmup-chunks", type=int, default=0,
                     help="warm replica 0 alone for this many chunks, then fork it and its stream to the others")
     args = ap.parse_args()
+    if not args.msglog and (args.placement_seed is not None or args.skew_max):
+        ap.error("--placement-seed and --skew-max go with --msglog")
 
+    import numpy as np
     import torch
 
     import primesim_amd as P
@@ -179,15 +201,30 @@ def main() -> int:
 
     um = P.UncoreManager()
     um.init(cfg, replicas=R)
-    dss = P.DeviceStreamSet(specs)
+    if args.msglog:
+        # the log's threads take their cores from the handle's scheduler as they appear (prime.cpp)
+        trace = P.msglog_read(args.msglog, um)
+        pseed = args.placement_seed or 0
+        seeds = [P.placement_seed(pseed, r) if args.placement_seed is not None else 0 for r in range(R)]
+        place = P.random_placements(R, nc, pseed) if args.placement_seed is not None else None
+        skews = None
+        if args.skew_max > 0:
+            skews = np.zeros((R, nc), dtype=np.int32)
+            for r in range(1, R):
+                skews[r] = np.random.default_rng([pseed, r]).integers(0, args.skew_max + 1, nc)
+        dss = P.DeviceTraceSet(trace, nc, R, placements=place, skews=skews)
+    else:
+        seeds = [args.seed_base + r for r in range(R)]
+        dss = P.DeviceStreamSet(specs)
     dsum = P.DeviceDelaySummary(R, num_cores=[nc] * R)
     dres = P.DeviceRunResults(um) if args.results else None
     dhist = P.DeviceDelayHistogram(R) if args.quantiles else None
     records = totals = qbuckets = total = None
     nlinks = 0
     try:
-        for prog, th in P.stream_threads(specs[0]):
-            um.allocCore(prog, th)
+        if not args.msglog:
+            for prog, th in P.stream_threads(specs[0]):
+                um.allocCore(prog, th)
         um.set_device_req_format(fmt)
         if args.warmup_chunks > 0:
             d_warm = d_off.clamp(max=n)                                 # replica 0: [0, n); every other: empty
@@ -196,7 +233,8 @@ def main() -> int:
                 dss.next_into(d_reqs.data_ptr(), n, fmt=fmt, stream_ptr=sp)
                 um.run_device(d_reqs.data_ptr(), d_warm.data_ptr(), d_del.data_ptr(), sp)
             um.fork_replica(0, stream_ptr=sp)
-            dss.fork(0, seeds=[args.seed_base + r for r in range(R)], stream_ptr=sp)
+            if not args.msglog:                                         # a trace set has one cursor: nothing to fork
+                dss.fork(0, seeds=seeds, stream_ptr=sp)
         for _ in range(args.chunks):
             dss.next_into(d_reqs.data_ptr(), n, fmt=fmt, stream_ptr=sp)
             um.run_device(d_reqs.data_ptr(), d_off.data_ptr(), d_del.data_ptr(), sp)
@@ -215,8 +253,9 @@ def main() -> int:
             _, qbuckets = dhist.quantiles(QUANTILE_PPM)                 # waits for the last add
             total = P.histogram_quantiles(dhist.total(), QUANTILE_PPM)
         stream.synchronize()
-        if int(dss.positions().min()) != n * (args.chunks + args.warmup_chunks):
-            print("ensemble_summary: a stream ended before its last chunk", file=sys.stderr)
+        served = dss.position() if args.msglog else int(dss.positions().min())
+        if served != n * (args.chunks + args.warmup_chunks):
+            print("ensemble_summary: a stream (or the message log) ended before its last chunk", file=sys.stderr)
             return 1
         flags = um.error_flags(R)
     finally:
@@ -228,7 +267,9 @@ def main() -> int:
         dss.close()
         um.close()
     for r in range(R):
-        line = replica_line(r, args.seed_base + r, summaries[r], int(flags[r]))
+        line = replica_line(r, seeds[r], summaries[r], int(flags[r]))
+        if args.msglog:
+            line["placement_seed"] = line.pop("seed")
         if qbuckets is not None:
             for c, name in enumerate(("read", "write")):
                 line[name].update(quantile_object(qbuckets[r][c]))
