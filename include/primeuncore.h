@@ -888,6 +888,75 @@ int       pu_dhist_host_quantiles(const uint64_t* hist_one_class, const uint32_t
 int       pu_dhist_bucket_of(int32_t d);
 int       pu_dhist_bucket_bounds(int bucket, int32_t* lo, int32_t* hi);
 
+/* Every replica's slowest requests kept on the device (no reference counterpart; one more
+ * stage on the same stream: ... -> pu_dsum_add -> pu_dhist_add -> pu_dtail_add).  The
+ * histograms say how large the tail is; these lists say which requests it is made of: core,
+ * address, issue time and place in the stream of the K worst reads and the K worst writes of
+ * every replica, still without a request or a delay on the host.  Every figure is an exact
+ * integer and depends only on the concatenation of what was added, so the device result
+ * equals the host fold (pu_dtail_host_add) bit for bit however the records were split into
+ * calls.
+ *
+ * The rule (primesim_amd/csrc/delay_tail_step.h):
+ *   set       `count` replicas and a list length k, 1 <= k <= PU_DTAIL_MAX_K, fixed at open.
+ *   class     as for pu_dsum_*: 0 = read, 1 = write (pu_req: mem_type == PU_WR).
+ *   seen      per replica, the records added since open or reset, both classes together.
+ *   position  adding [begin, end) gives record i the position seen + (i - begin), then
+ *             raises seen by end - begin; begin >= end adds nothing.
+ *   order     entry x is better than entry y when x.delay > y.delay, or at equal delays when
+ *             x.position < y.position.  Positions of a replica are distinct: a strict total
+ *             order.  Delays of 0, negative delays and INT32_MIN are ordinary values.
+ *   list      per replica and class the best min(k, records of the class seen) entries, best
+ *             first; the entries past that count are all-zero bytes.
+ *   total     the best k entries over replicas [first, first + n), per class, by delay
+ *             descending, then replica ascending, then position ascending.
+ *
+ * pu_dtail_open: `count` replicas with lists of k entries on `device`; 64 * k + 16 B of device
+ * memory per replica plus the partial lists of the ensemble total.  NULL + pu_last_error() on
+ * failure (count < 1 or k outside 1 .. PU_DTAIL_MAX_K: before a device is touched; "no HIP
+ * device" where there is none: the set has no CPU fallback).
+ *
+ * pu_dtail_add: replica r adds records [d_begin[r], d_end[r]); the arguments, their checks
+ * (d_reqs 16-byte aligned) and the ordering are pu_dsum_add's and pu_dhist_add's, so one pair
+ * of index arrays serves all three calls.  The request array is read again only for the
+ * entries that enter a list.
+ *
+ * pu_dtail_read: the lists of replicas [first, first + n): out holds n * 2 * k entries,
+ * [replica][class][rank], count_out n * 2 counts.  pu_dtail_read_total: the ensemble total of
+ * replicas [first, first + n), formed when read by two launches without atomics on the set's
+ * own stream: out holds 2 * k entries, replica_out the replica of each (-1 past the count),
+ * count_out two counts; n = 0 gives empty lists.  pu_dtail_reset: every list empty and every
+ * seen 0, the state after open.  pu_dtail_state_bytes: device memory the set holds.
+ * pu_dtail_k: the list length (0 for NULL).  Reading, resetting and closing wait only for the
+ * work of this set.  A NULL set: PU_EINVAL, 0, no-op; first < 0, n < 0 or a NULL output with
+ * n > 0: PU_EINVAL; first + n > count: PU_ERANGE.
+ *
+ * Host twin, no device needed.  pu_dtail_host_add: n records added to one replica's lists
+ * (entries [2][k], counts [2] and *seen, all zeroed by the caller before the first call). */
+#define PU_DTAIL_MAX_K 64
+typedef struct pu_dtail_entry {
+    uint64_t addr;      /* pu_req.addr / pu_req16.a */
+    int64_t  timer;     /* the recorded timer (pu_req.timer / PU_REQ16_TIMER) */
+    uint64_t position;  /* as above */
+    int32_t  delay;
+    int32_t  core;      /* pu_req.core as it stands / PU_REQ16_CORE; not range-checked */
+} pu_dtail_entry;       /* 32 bytes */
+
+typedef struct pu_dtail pu_dtail;
+pu_dtail* pu_dtail_open(int count, int k, int device);
+void      pu_dtail_close(pu_dtail* s);
+int       pu_dtail_add(pu_dtail* s, const void* d_reqs, int fmt, const int32_t* d_delay,
+                       const uint64_t* d_begin, const uint64_t* d_end, void* hip_stream);
+int       pu_dtail_read(pu_dtail* s, int first, int n, pu_dtail_entry* out /*[n][2][k]*/,
+                        uint32_t* count_out /*[n][2]*/);
+int       pu_dtail_read_total(pu_dtail* s, int first, int n, pu_dtail_entry* out /*[2][k]*/,
+                              int32_t* replica_out /*[2][k]*/, uint32_t* count_out /*[2]*/);
+int       pu_dtail_reset(pu_dtail* s);
+uint64_t  pu_dtail_state_bytes(const pu_dtail* s);
+int       pu_dtail_k(const pu_dtail* s);
+int       pu_dtail_host_add(pu_dtail_entry* entries /*[2][k]*/, uint32_t* counts /*[2]*/, uint64_t* seen,
+                            int k, const void* reqs, int fmt, const int32_t* delays, size_t n);
+
 /* Trace files ("PUTRACE1": header, thread table, pu_req records). */
 int pu_trace_write(const char* path, const pu_req* reqs, size_t n,
                    const int32_t* thread_prog, const int32_t* thread_id, int num_threads);

@@ -5,14 +5,14 @@ this package is its Python host mirror (`uncore.UncoreManager`), the config_prim
 schema (`config`) and the ctypes ABI definitions (`_abi`).
 """
 from . import _abi, config  # noqa: F401
-from .uncore import (DeviceDelayHistogram, DeviceDelaySummary, DeviceRunResults, DeviceStreamSet, DeviceTraceSet, InsMem, StreamSet, StreamSpec, UncoreError, UncoreManager, config_from_dict,  # noqa: F401
+from .uncore import (DeviceDelayHistogram, DeviceDelaySummary, DeviceDelayTail, DeviceRunResults, DeviceStreamSet, DeviceTraceSet, InsMem, StreamSet, StreamSpec, UncoreError, UncoreManager, config_from_dict,  # noqa: F401
                      generate_stream, load_config, msglog_from_stream, msglog_read, parse_config,
                      pack_req16, stream_fits_req16, stream_threads, summarize_delays, MsgLogWriter,
                      host_run_results, queue_ends, delay_histogram, histogram_quantiles, dhist_bucket_of,
-                     dhist_bucket_bounds, place_trace, placement_seed, random_placements)
+                     dhist_bucket_bounds, delay_tail, place_trace, placement_seed, random_placements)
 
-__all__ = ["DeviceDelayHistogram", "DeviceDelaySummary", "DeviceRunResults", "DeviceStreamSet", "DeviceTraceSet", "InsMem", "StreamSet", "StreamSpec", "UncoreError", "UncoreManager", "config_from_dict", "generate_stream",
+__all__ = ["DeviceDelayHistogram", "DeviceDelaySummary", "DeviceDelayTail", "DeviceRunResults", "DeviceStreamSet", "DeviceTraceSet", "InsMem", "StreamSet", "StreamSpec", "UncoreError", "UncoreManager", "config_from_dict", "generate_stream",
            "load_config", "msglog_from_stream", "msglog_read", "MsgLogWriter", "pack_req16", "parse_config",
            "stream_fits_req16", "stream_threads", "summarize_delays", "host_run_results", "queue_ends",
            "delay_histogram", "histogram_quantiles", "dhist_bucket_of", "dhist_bucket_bounds", "place_trace",
-           "placement_seed", "random_placements"]
+           "placement_seed", "random_placements", "delay_tail"]

@@ -23,6 +23,7 @@ PU_REQ_FMT_32, PU_REQ_FMT_16 = 0, 1      # device request records: pu_req, pu_re
 
 PU_DSUM_BUCKETS = 32                     # delay summaries (pu_dsum_*)
 PU_DHIST_SUB_BITS, PU_DHIST_BUCKETS, PU_DHIST_MAX_Q = 5, 864, 8     # log-linear delay histograms (pu_dhist_*)
+PU_DTAIL_MAX_K = 64                      # the longest list of slowest requests (pu_dtail_*)
 
 PU_ERRF_CORE_RANGE = 1 << 0
 PU_ERRF_WB_MISS = 1 << 1
@@ -134,6 +135,11 @@ class DhistQuantile(C.Structure):       # pu_dhist_quantile
     _fields_ = [("count", C.c_uint64), ("bucket", C.c_int32 * PU_DHIST_MAX_Q)]
 
 
+class DtailEntry(C.Structure):          # pu_dtail_entry
+    _fields_ = [("addr", C.c_uint64), ("timer", C.c_int64), ("position", C.c_uint64), ("delay", C.c_int32),
+                ("core", C.c_int32)]
+
+
 class DresReplica(C.Structure):         # pu_dres_replica
     _fields_ = [
         ("stats", Stats), ("processed", C.c_uint64), ("halted", C.c_int32), ("cores_done", C.c_int32),
@@ -178,6 +184,9 @@ assert DSUM_DTYPE.itemsize == C.sizeof(DsumReplica) == 568
 # pu_dhist_quantile as a numpy structured dtype
 DHIST_Q_DTYPE = np.dtype([("count", "<u8"), ("bucket", "<i4", (PU_DHIST_MAX_Q,))])
 assert DHIST_Q_DTYPE.itemsize == C.sizeof(DhistQuantile) == 40
+# pu_dtail_entry as a numpy structured dtype
+DTAIL_DTYPE = np.dtype([("addr", "<u8"), ("timer", "<i8"), ("position", "<u8"), ("delay", "<i4"), ("core", "<i4")])
+assert DTAIL_DTYPE.itemsize == C.sizeof(DtailEntry) == 32
 # pu_level_stats / pu_stats / pu_dres_replica as numpy structured dtypes
 LEVEL_STATS_DTYPE = np.dtype([("ins", "<u8"), ("miss", "<u8"), ("evict", "<u8"), ("wb", "<u8")])
 STATS_DTYPE = np.dtype(

@@ -157,6 +157,16 @@ def lib() -> C.CDLL:
         "pu_dhist_host_quantiles": (C.c_int, [P(C.c_uint64), P(C.c_uint32), C.c_int, P(C.c_uint64), P(C.c_int32)]),
         "pu_dhist_bucket_of": (C.c_int, [C.c_int32]),
         "pu_dhist_bucket_bounds": (C.c_int, [C.c_int, P(C.c_int32), P(C.c_int32)]),
+        "pu_dtail_open": (C.c_void_p, [C.c_int, C.c_int, C.c_int]),
+        "pu_dtail_close": (None, [C.c_void_p]),
+        "pu_dtail_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "pu_dtail_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(A.DtailEntry), P(C.c_uint32)]),
+        "pu_dtail_read_total": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(A.DtailEntry), P(C.c_int32), P(C.c_uint32)]),
+        "pu_dtail_reset": (C.c_int, [C.c_void_p]),
+        "pu_dtail_state_bytes": (C.c_uint64, [C.c_void_p]),
+        "pu_dtail_k": (C.c_int, [C.c_void_p]),
+        "pu_dtail_host_add": (C.c_int, [P(A.DtailEntry), P(C.c_uint32), P(C.c_uint64), C.c_int, C.c_void_p, C.c_int,
+                                        P(C.c_int32), C.c_size_t]),
         "pu_dres_open": (C.c_void_p, [C.c_void_p, C.c_int]),
         "pu_dres_close": (None, [C.c_void_p]),
         "pu_dres_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -805,6 +815,102 @@ class DeviceDelayHistogram(_Owner):
         rc = lib().pu_dhist_reset(self._handle())
         if rc != 0:
             raise UncoreError(f"pu_dhist_reset: {last_error()} ({rc})")
+
+
+# ---------------------------------------------------------------- slowest requests
+def delay_tail(reqs: np.ndarray, delays: np.ndarray, k: int, fmt: int = A.PU_REQ_FMT_32, acc=None):
+    """The host fold of (request, delay) pairs into one replica's lists of slowest requests
+    (pu_dtail_host_add; the rule is in include/primeuncore.h): returns (entries, counts, seen),
+    entries A.DTAIL_DTYPE [2, k] (reads and writes apart, best first, zero past the count),
+    counts uint32 [2] and seen, the records added so far.  acc, a triple an earlier call
+    returned for the same k, is continued (and left unchanged).  reqs as for
+    summarize_delays.  Needs no device."""
+    n = len(delays)
+    if fmt == A.PU_REQ_FMT_16:
+        assert reqs.dtype == np.uint64 and reqs.shape == (n, 2)
+    else:
+        assert reqs.dtype == A.REQ_DTYPE and reqs.shape == (n,)
+    reqs = np.ascontiguousarray(reqs)
+    delays = np.ascontiguousarray(delays, dtype=np.int32)
+    k = int(k)
+    if acc is None:
+        entries, counts, seen = np.zeros((2, max(k, 1)), dtype=A.DTAIL_DTYPE), np.zeros(2, dtype=np.uint32), C.c_uint64(0)
+    else:
+        entries, counts, seen = acc[0].copy(), acc[1].copy(), C.c_uint64(int(acc[2]))
+        if entries.shape != (2, k) or entries.dtype != A.DTAIL_DTYPE or counts.shape != (2,) or counts.dtype != np.uint32:
+            raise UncoreError(f"delay_tail: acc is not the result of a call with k = {k}")
+    rc = lib().pu_dtail_host_add(_as(entries, A.DtailEntry), _as(counts, C.c_uint32), C.byref(seen), k,
+                                 reqs.ctypes.data, fmt, _as(delays, C.c_int32), n)
+    if rc != 0:
+        raise UncoreError(f"pu_dtail_host_add: {last_error()} ({rc})")
+    return entries, counts, int(seen.value)
+
+
+class DeviceDelayTail(_Owner):
+    """Per-replica lists of the k slowest reads and the k slowest writes kept on the device
+    (pu_dtail_*): `add` offers every replica's records [begin[r], end[r]) of device request and
+    delay arrays to its lists, bit for bit what delay_tail gives; `total` is the best k of the
+    ensemble, formed on the device.  Pointers are plain integers (tensor.data_ptr()).
+    Needs a GPU: there is no host fallback."""
+    _close, _no_handle = "pu_dtail_close", "DeviceDelayTail is closed"
+
+    def __init__(self, count: int, k: int = 16, device: int = 0):
+        self._n, self._k = count, k
+        h = lib().pu_dtail_open(count, k, device)
+        if not h:
+            raise UncoreError(f"pu_dtail_open: {last_error()}")
+        self._h = h
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def k(self) -> int:
+        """Entries a list holds at most."""
+        return int(lib().pu_dtail_k(self._handle()))
+
+    state_bytes = _state_bytes("pu_dtail_state_bytes", "Device memory the set holds.")
+
+    def add(self, d_reqs_ptr: int, d_delay_ptr: int, d_begin_ptr: int, d_end_ptr: int, fmt: int = A.PU_REQ_FMT_32,
+            stream_ptr: int = 0) -> None:
+        """As DeviceDelaySummary.add: asynchronous on stream_ptr (0 is the set's own stream);
+        d_begin / d_end: device uint64, one entry per replica, in records."""
+        rc = lib().pu_dtail_add(self._handle(), d_reqs_ptr or None, fmt, d_delay_ptr or None, d_begin_ptr or None,
+                                d_end_ptr or None, stream_ptr or None)
+        if rc != 0:
+            raise UncoreError(f"pu_dtail_add: {last_error()} ({rc})")
+
+    def read(self, first: int = 0, n: Optional[int] = None) -> tuple[np.ndarray, np.ndarray]:
+        """(entries, counts) of replicas [first, first + n): A.DTAIL_DTYPE [n, 2, k], best first and zero
+        past the count, and uint32 [n, 2] (waits for the set's calls)."""
+        h = self._handle()
+        n = self._n - first if n is None else n
+        entries = np.zeros((max(n, 0), 2, self._k), dtype=A.DTAIL_DTYPE)
+        counts = np.zeros((max(n, 0), 2), dtype=np.uint32)
+        rc = lib().pu_dtail_read(h, first, n, _as(entries, A.DtailEntry), _as(counts, C.c_uint32))
+        if rc != 0:
+            raise UncoreError(f"pu_dtail_read: {last_error()} ({rc})")
+        return entries, counts
+
+    def total(self, first: int = 0, n: Optional[int] = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(entries, replicas, counts) of the best k over replicas [first, first + n), per class:
+        A.DTAIL_DTYPE [2, k], int32 [2, k] (-1 past the count) and uint32 [2]; by delay descending,
+        then replica, then position.  Lists of different ranks merge by the same order on the host."""
+        h = self._handle()
+        n = self._n - first if n is None else n
+        entries = np.zeros((2, self._k), dtype=A.DTAIL_DTYPE)
+        replicas = np.full((2, self._k), -1, dtype=np.int32)
+        counts = np.zeros(2, dtype=np.uint32)
+        rc = lib().pu_dtail_read_total(h, first, n, _as(entries, A.DtailEntry), _as(replicas, C.c_int32),
+                                       _as(counts, C.c_uint32))
+        if rc != 0:
+            raise UncoreError(f"pu_dtail_read_total: {last_error()} ({rc})")
+        return entries, replicas, counts
+
+    def reset(self) -> None:
+        rc = lib().pu_dtail_reset(self._handle())
+        if rc != 0:
+            raise UncoreError(f"pu_dtail_reset: {last_error()} ({rc})")
 
 
 QUEUE_KINDS = ("x", "y", "z", "bus")     # pu_config_queue_ends: kind 0 .. 3

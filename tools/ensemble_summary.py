@@ -25,9 +25,16 @@ quantile (exact below 64 cycles, within 3.2 % above; null for an empty class), r
 from the histogram on the device, and one last line carries the same for the histogram
 summed over the replicas.
 
+With --tail K the K slowest reads and the K slowest writes of every replica are kept on the
+device too (DeviceDelayTail.add on the same stream, after the summary's add and the
+histogram's; 64 K + 16 B per replica): every replica's "read" and "write" objects gain
+"slowest", a list of {"delay", "core", "addr", "timer", "position"}, the worst first
+(position: the request's place among the replica's measured requests), and one last line
+carries the K slowest of the whole ensemble with the "replica" of each.
+
 With --warmup-chunks K the cold start is simulated once: replica 0 alone runs K chunks of
-stream 0 (the other replicas get empty ranges; nothing goes to the summaries or
-histograms), then every other replica becomes a copy of it (UncoreManager.fork_replica)
+stream 0 (the other replicas get empty ranges; nothing goes to the summaries,
+histograms or lists of the slowest), then every other replica becomes a copy of it (UncoreManager.fork_replica)
 and every other stream continues from stream 0's position with its own seed
 (DeviceStreamSet.fork), all on the same stream, and the --chunks measured chunks run as
 usual.  The forks share their warm-up: they are correlated until their own streams have
@@ -114,6 +121,25 @@ def total_line(replicas: int, counts, buckets) -> dict:
                           for c, name in enumerate(("read", "write"))}}
 
 
+def slowest_list(entries, count, replicas=None) -> list:
+    """One class's list of slowest requests (A.DTAIL_DTYPE entries, the first `count` of them), the worst first."""
+    out = []
+    for i in range(int(count)):
+        e = entries[i]
+        item = {"delay": int(e["delay"]), "core": int(e["core"]), "addr": hex(int(e["addr"])), "timer": int(e["timer"]),
+                "position": int(e["position"])}
+        if replicas is not None:
+            item = {"replica": int(replicas[i]), **item}
+        out.append(item)
+    return out
+
+
+def tail_total_line(replicas: int, entries, reps, counts) -> dict:
+    """The last line of --tail: the slowest requests of the ensemble (DeviceDelayTail.total), per class."""
+    return {"replicas": replicas,
+            "slowest": {name: slowest_list(entries[c], counts[c], reps[c]) for c, name in enumerate(("read", "write"))}}
+
+
 def link_entry(cfg, q: int, visits: int, block_visits=None) -> dict:
     """Queue q of the configuration with its ends (pu_config_queue_ends) and its visit count."""
     import primesim_amd as P
@@ -166,11 +192,15 @@ def main() -> int:
     ap.add_argument("--results", action="store_true", help="also gather the end-of-run results on the device")
     ap.add_argument("--quantiles", action="store_true",
                     help="also keep a log-linear delay histogram on the device and print p50 / p90 / p99 / p99.9")
+    ap.add_argument("--tail", type=int, default=0, metavar="K",
+                    help="also keep every replica's K slowest reads and writes on the device (1 .. 64)")
     ap.add_argument("--warmup-chunks", type=int, default=0,
                     help="warm replica 0 alone for this many chunks, then fork it and its stream to the others")
     args = ap.parse_args()
     if not args.msglog and (args.placement_seed is not None or args.skew_max):
         ap.error("--placement-seed and --skew-max go with --msglog")
+    if not 0 <= args.tail <= 64:
+        ap.error("--tail takes a list length of 1 .. 64")
 
     import numpy as np
     import torch
@@ -219,7 +249,8 @@ def main() -> int:
     dsum = P.DeviceDelaySummary(R, num_cores=[nc] * R)
     dres = P.DeviceRunResults(um) if args.results else None
     dhist = P.DeviceDelayHistogram(R) if args.quantiles else None
-    records = totals = qbuckets = total = None
+    dtail = P.DeviceDelayTail(R, args.tail) if args.tail else None
+    records = totals = qbuckets = total = tails = tail_total = None
     nlinks = 0
     try:
         if not args.msglog:
@@ -242,6 +273,9 @@ def main() -> int:
             if dhist is not None:
                 dhist.add(d_reqs.data_ptr(), d_del.data_ptr(), d_off.data_ptr(), d_off.data_ptr() + 8, fmt=fmt,
                           stream_ptr=sp)
+            if dtail is not None:
+                dtail.add(d_reqs.data_ptr(), d_del.data_ptr(), d_off.data_ptr(), d_off.data_ptr() + 8, fmt=fmt,
+                          stream_ptr=sp)
         if dres is not None:
             dres.gather(stream_ptr=sp)                                  # one launch, after the last chunk
         summaries = dsum.read()                                         # waits for the last add
@@ -252,6 +286,9 @@ def main() -> int:
         if dhist is not None:
             _, qbuckets = dhist.quantiles(QUANTILE_PPM)                 # waits for the last add
             total = P.histogram_quantiles(dhist.total(), QUANTILE_PPM)
+        if dtail is not None:
+            tails = dtail.read()                                        # waits for the last add
+            tail_total = dtail.total()
         stream.synchronize()
         served = dss.position() if args.msglog else int(dss.positions().min())
         if served != n * (args.chunks + args.warmup_chunks):
@@ -263,6 +300,8 @@ def main() -> int:
             dres.close()
         if dhist is not None:
             dhist.close()
+        if dtail is not None:
+            dtail.close()
         dsum.close()
         dss.close()
         um.close()
@@ -273,6 +312,9 @@ def main() -> int:
         if qbuckets is not None:
             for c, name in enumerate(("read", "write")):
                 line[name].update(quantile_object(qbuckets[r][c]))
+        if tails is not None:
+            for c, name in enumerate(("read", "write")):
+                line[name]["slowest"] = slowest_list(tails[0][r][c], tails[1][r][c])
         if records is not None:
             line["results"] = results_object(cfg, records[r])
         print(json.dumps(line))
@@ -280,6 +322,8 @@ def main() -> int:
         print(json.dumps({"replicas": R, "hottest_links": hottest_links(cfg, totals[0], totals[1], nlinks)}))
     if total is not None:
         print(json.dumps(total_line(R, total[0], total[1])))
+    if tail_total is not None:
+        print(json.dumps(tail_total_line(R, *tail_total)))
     return 0
 
 
