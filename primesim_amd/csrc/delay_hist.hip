@@ -13,11 +13,8 @@
 //
 // dhist_add_kernel<FMT>: one launch per call, one workgroup of 256 per replica,
 // which owns that replica's row for the launch; no atomics on device memory.
-//   * The loads are dsum_add_kernel's without tables: lanes take consecutive records,
-//     four per lane and trip (a trip's loads are issued before any is used); of a
-//     pu_req16 only b (8 B), of a pu_req its last word (8 B: mem_type | ...; the class is
-//     all this kernel needs of a record, so not the 16 B that carry the core id too), of
-//     the delays one dword.
+//   * The range and the loads are delay_stage.h's RecordSource; the class is all this
+//     kernel needs of a record, so 8 B of it.
 //   * The counters are 2 x 864 64-bit LDS counters of the workgroup (13,824 B static).
 //     A record's key is class * 864 + bucket; every record in the range does one LDS
 //     atomic add on its counter.  Reducing equal keys in the wave first (broadcast the
@@ -45,18 +42,14 @@
 #include "../../include/primeuncore.h"
 #include "common.h"
 #include "delay_hist_step.h"
+#include "delay_stage.h"
 #include "device_set.h"
 
 using namespace pu_delay_hist;
-using pu_delay_sum::class_of_mem_type;
-using pu_delay_sum::class_of_req16_b;
 using pu::round16;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kUnroll = 4;                          // records / replicas per lane and trip
 constexpr int kKeys = 2 * PU_DHIST_BUCKETS;         // counters of a replica
 constexpr int kPerLane = 14;                        // buckets a lane of the quantile scan takes
 constexpr int kGroups = 120;                        // replica groups of the total's first pass, at most
@@ -65,18 +58,11 @@ constexpr int kTiles = (kKeys + kThreads - 1) / kThreads;
 static_assert(64 * kPerLane >= PU_DHIST_BUCKETS, "a wave covers a class");
 static_assert(sizeof(pu_dhist_quantile) == 40, "count and eight buckets, no padding");
 
-typedef unsigned long long u64;
-
 // the quantiles of one call
 struct DhistQ {
     uint32_t ppm[PU_DHIST_MAX_Q];
     int32_t nq;
 };
-
-__global__ __launch_bounds__(kThreads) void dhist_reset_kernel(u64* hist, size_t words) {
-    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i < words) hist[i] = 0;
-}
 
 template <int FMT>
 __global__ __launch_bounds__(kThreads) void dhist_add_kernel(u64* __restrict__ hist, const void* __restrict__ reqs,
@@ -86,40 +72,25 @@ __global__ __launch_bounds__(kThreads) void dhist_add_kernel(u64* __restrict__ h
     __shared__ u64 s_hist[kKeys];
 
     const int r = (int)blockIdx.x;
-    const uint64_t b = d_begin[r], e = d_end[r];
-    if (b >= e) return;   // the whole workgroup: nothing to add
-    const uint64_t len = e - b;
+    const RecordRange rg(d_begin, d_end);
+    if (rg.empty()) return;
+    const uint64_t len = rg.len();
     const int tid = (int)threadIdx.x;
 
 #pragma unroll
     for (int k = tid; k < kKeys; k += kThreads) s_hist[k] = 0;
     __syncthreads();
 
-    const int32_t* const dl = delay + b;
-    // the word that holds the class: pu_req16.b, or mem_type | ... of a pu_req (its last 8 bytes)
-    constexpr int kStride = FMT == PU_REQ_FMT_16 ? 2 : 4;
-    const uint64_t* const wd = (const uint64_t*)reqs + (uint64_t)kStride * b + (kStride - 1);
-
-    for (uint64_t base = 0; base < len; base += (uint64_t)kThreads * kUnroll) {
+    const RecordSource<FMT, false> src(reqs, delay, rg.b, len);
+    for (uint64_t base = 0; base < len; base += kTrip) {
         int32_t d[kUnroll];
         u64 w[kUnroll];
         bool valid[kUnroll];
 #pragma unroll
-        for (int u = 0; u < kUnroll; u++) {
-            const uint64_t i = base + (uint64_t)(u * kThreads + tid);
-            valid[u] = i < len;
-            d[u] = 0;
-            w[u] = 0;
-            if (valid[u]) {
-                d[u] = dl[i];
-                w[u] = wd[(uint64_t)kStride * i];
-            }
-        }
+        for (int u = 0; u < kUnroll; u++) valid[u] = src.load(base + (uint64_t)(u * kThreads + tid), d[u], w[u]);
 #pragma unroll
-        for (int u = 0; u < kUnroll; u++) {
-            const int cls = FMT == PU_REQ_FMT_16 ? class_of_req16_b(w[u]) : class_of_mem_type((uint32_t)(w[u] & 0xFFu));
-            if (valid[u]) atomicAdd(&s_hist[key_of(cls, d[u])], 1ull);
-        }
+        for (int u = 0; u < kUnroll; u++)
+            if (valid[u]) atomicAdd(&s_hist[key_of(src.cls(w[u]), d[u])], 1ull);
     }
     __syncthreads();   // the counters are complete
 
@@ -220,33 +191,6 @@ struct pu_dhist : pu::DeviceSet {
     u64* tot = nullptr;
 };
 
-namespace {
-
-int launch_reset(pu_dhist* s) {
-    int rc = s->order_before(s->stream);
-    if (rc) return rc;
-    const size_t words = (size_t)s->count * kKeys;
-    hipLaunchKernelGGL(dhist_reset_kernel, dim3((unsigned)((words + kThreads - 1) / kThreads)), dim3(kThreads), 0, s->stream,
-                       s->hist, words);
-    return s->record_after(s->stream, "pu_dhist_reset");
-}
-
-template <int FMT>
-void launch_add(pu_dhist* s, hipStream_t st, const void* d_reqs, const int32_t* d_delay, const uint64_t* d_begin,
-                const uint64_t* d_end) {
-    hipLaunchKernelGGL((dhist_add_kernel<FMT>), dim3((unsigned)s->count), dim3(kThreads), 0, st, s->hist, d_reqs,
-                       d_delay, d_begin, d_end);
-}
-
-// first, n against the set; 1: nothing to do (n == 0), 0: go on, else PU_E*
-int check_range(const pu_dhist* s, int first, int n, const void* out, const char* who) {
-    if (!s || first < 0 || n < 0 || (!out && n)) return pu::set_error(PU_EINVAL, std::string(who) + ": bad arguments");
-    if ((int64_t)first + n > s->count) return pu::set_error(PU_ERANGE, "more replicas than the set holds");
-    return n == 0 ? 1 : 0;
-}
-
-}  // namespace
-
 extern "C" {
 
 pu_dhist* pu_dhist_open(int count, int device) {
@@ -281,22 +225,14 @@ void pu_dhist_close(pu_dhist* s) { pu::close_set(s); }
 
 int pu_dhist_add(pu_dhist* s, const void* d_reqs, int fmt, const int32_t* d_delay, const uint64_t* d_begin,
                  const uint64_t* d_end, void* hip_stream) {
-    if (!s || !pu::req_fmt_ok(fmt) || !d_reqs || !d_delay || !d_begin || !d_end || ((uintptr_t)d_reqs & 15))
-        return pu::set_error(PU_EINVAL, "pu_dhist_add: bad arguments");
-    int rc = s->use();
-    if (rc) return rc;
-    hipStream_t st = s->pick(hip_stream);
-    rc = s->order_before(st);
-    if (rc) return rc;
-    if (fmt == PU_REQ_FMT_16)
-        launch_add<PU_REQ_FMT_16>(s, st, d_reqs, d_delay, d_begin, d_end);
-    else
-        launch_add<PU_REQ_FMT_32>(s, st, d_reqs, d_delay, d_begin, d_end);
-    return s->record_after(st, "pu_dhist_add");
+    return delay_add(s, "pu_dhist_add", d_reqs, fmt, d_delay, d_begin, d_end, hip_stream, [&](auto F, hipStream_t st) {
+        hipLaunchKernelGGL((dhist_add_kernel<decltype(F)::value>), dim3((unsigned)s->count), dim3(kThreads), 0, st, s->hist,
+                           d_reqs, d_delay, d_begin, d_end);
+    });
 }
 
 int pu_dhist_read(pu_dhist* s, int first, int n, uint64_t* out) {
-    const int rc = check_range(s, first, n, out, "pu_dhist_read");
+    const int rc = pu::replica_range(s ? s->count : 0, first, n, out != nullptr, "pu_dhist_read");
     if (rc) return rc < 0 ? rc : 0;
     return s->read_back(
         [&](hipStream_t st) {
@@ -307,7 +243,7 @@ int pu_dhist_read(pu_dhist* s, int first, int n, uint64_t* out) {
 }
 
 int pu_dhist_quantiles(pu_dhist* s, int first, int n, const uint32_t* ppm, int nq, pu_dhist_quantile* out) {
-    int rc = check_range(s, first, n, out, "pu_dhist_quantiles");
+    int rc = pu::replica_range(s ? s->count : 0, first, n, out != nullptr, "pu_dhist_quantiles");
     if (rc < 0) return rc;
     if (!ppm || nq < 1 || nq > PU_DHIST_MAX_Q)
         return pu::set_error(PU_EINVAL, "pu_dhist_quantiles: between 1 and " + std::to_string(PU_DHIST_MAX_Q) + " quantiles");
@@ -338,13 +274,14 @@ int pu_dhist_quantiles(pu_dhist* s, int first, int n, const uint32_t* ppm, int n
 }
 
 int pu_dhist_read_total(pu_dhist* s, int first, int n, uint64_t* out) {
-    if (!s || first < 0 || n < 0 || !out) return pu::set_error(PU_EINVAL, "pu_dhist_read_total: bad arguments");
-    if ((int64_t)first + n > s->count) return pu::set_error(PU_ERANGE, "more replicas than the set holds");
-    if (n == 0) {
+    // n == 0 fills the output too: without it there is nothing to call, as without a set
+    int rc = pu::replica_range(s && out ? s->count : 0, first, n, true, "pu_dhist_read_total");
+    if (rc < 0) return rc;
+    if (rc) {
         std::memset(out, 0, (size_t)kKeys * 8);
         return 0;
     }
-    int rc = s->use();
+    rc = s->use();
     if (rc) return rc;
     hipStream_t st = s->stream;
     rc = s->order_before(st);
@@ -362,8 +299,7 @@ int pu_dhist_read_total(pu_dhist* s, int first, int n, uint64_t* out) {
 
 int pu_dhist_reset(pu_dhist* s) {
     if (!s) return pu::set_error(PU_EINVAL, "pu_dhist_reset: no set");
-    int rc = s->use();
-    return rc ? rc : launch_reset(s);   // on the set's own stream, after the set's last call
+    return reset_words(s, s->hist, (size_t)s->count * kKeys, "pu_dhist_reset");
 }
 
 uint64_t pu_dhist_state_bytes(const pu_dhist* s) { return s ? (uint64_t)s->bytes : 0; }
@@ -371,12 +307,7 @@ uint64_t pu_dhist_state_bytes(const pu_dhist* s) { return s ? (uint64_t)s->bytes
 int pu_dhist_host_add(uint64_t* hist, const void* reqs, int fmt, const int32_t* delays, size_t n) {
     if (!hist || !pu::req_fmt_ok(fmt) || (n && (!reqs || !delays)))
         return pu::set_error(PU_EINVAL, "pu_dhist_host_add: bad arguments");
-    const pu_req* r32 = (const pu_req*)reqs;
-    const pu_req16* r16 = (const pu_req16*)reqs;
-    for (size_t i = 0; i < n; i++) {
-        const int cls = fmt == PU_REQ_FMT_16 ? class_of_req16_b(r16[i].b) : class_of_mem_type(r32[i].mem_type);
-        hist[key_of(cls, delays[i])]++;
-    }
+    for (size_t i = 0; i < n; i++) hist[key_of(pu_delay_record::class_at(reqs, fmt, i), delays[i])]++;
     return 0;
 }
 

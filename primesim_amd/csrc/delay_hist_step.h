@@ -3,7 +3,7 @@
 // pu_dhist_host_quantiles) and the device kernels (delay_hist.hip): a delay's
 // fine bucket and its inverse, the fold of a fine bucket down to the power-of-two
 // bucket of the delay summaries, the rank of a quantile and the walk that answers
-// it.  A record's class is the delay summaries' (pu_delay_sum::class_of_*).
+// it.  A record's class is delay_record_step.h's.
 // Everything here compiles as plain C++ on the host (PU_HD is empty there) and as
 // __host__ __device__ under hipcc's HIP mode.  All of it is integer and
 // independent of order, so any split of the work gives the same bits.
@@ -13,7 +13,8 @@
 #include <cstdint>
 
 #include "../../include/primeuncore.h"
-#include "delay_sum_step.h"
+#include "delay_record_step.h"
+#include "delay_sum_step.h"   // pu_delay_sum::bucket_of, the bucket coarse_of folds down to
 #include "pu_hd.h"
 
 namespace pu_delay_hist {

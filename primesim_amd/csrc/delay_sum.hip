@@ -14,10 +14,8 @@
 // Kernel: one launch per call, one workgroup of 256 per replica, which owns that
 // replica's rows for the launch: nothing is accumulated across workgroups and the
 // running summary is updated by plain read-modify-write at the end.
-//   * Lanes take consecutive records, four per lane and trip (the loads of a trip
-//     are issued before any is used).  Of a pu_req16 only b is loaded (8 B), of a
-//     pu_req its second half (16 B: core | prog_id, mem_type | ...), of the delays
-//     one dword per lane, naturally aligned whatever d_begin is.
+//   * The range and the loads are delay_stage.h's RecordSource, asked for the core
+//     id as well as the class.
 //   * sum, min, max and the out-of-range count live in per-lane registers and meet
 //     once, after the loop: a wave reduction by __shfl_xor, then across the four
 //     waves through LDS.
@@ -45,6 +43,7 @@
 
 #include "../../include/primeuncore.h"
 #include "common.h"
+#include "delay_stage.h"
 #include "delay_sum_step.h"
 #include "device_set.h"
 
@@ -53,9 +52,6 @@ using pu::round16;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kUnroll = 4;        // records per lane and trip
 constexpr int kLdsCores = 1024;   // the largest per-core table kept in LDS
 
 // what a wave leaves for the combine across waves
@@ -70,8 +66,6 @@ constexpr int kOffHist = 0;     // unsigned long long [2][32]
 constexpr int kOffPart = 512;   // WavePart [kWaves]
 constexpr int kOffTab = 768;    // unsigned long long count[nc], then sum[nc]
 static_assert(sizeof(WavePart) * kWaves <= kOffTab - kOffPart, "the wave partials fit their slot");
-
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
 __global__ __launch_bounds__(kThreads) void dsum_reset_kernel(pu_dsum_replica* rep, const int32_t* ncores,
                                                                const uint64_t* core0, uint64_t* g_cnt, int64_t* g_sum) {
@@ -106,9 +100,9 @@ __global__ __launch_bounds__(kThreads) void dsum_add_kernel(pu_dsum_replica* rep
     unsigned long long* const s_tab = (unsigned long long*)(s_mem + kOffTab);
 
     const int r = (int)blockIdx.x;
-    const uint64_t b = d_begin[r], e = d_end[r];
-    if (b >= e) return;   // the whole workgroup: nothing to add
-    const uint64_t len = e - b;
+    const RecordRange rg(d_begin, d_end);
+    if (rg.empty()) return;
+    const uint64_t len = rg.len();
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nc = CORES ? ncores[r] : 0;
     const uint32_t limit = core_limit(nc);
@@ -124,28 +118,15 @@ __global__ __launch_bounds__(kThreads) void dsum_add_kernel(pu_dsum_replica* rep
     long long sum0 = 0, sum1 = 0;
     unsigned long long oor = 0;
     int32_t mn0 = INT32_MAX, mn1 = INT32_MAX, mx0 = INT32_MIN, mx1 = INT32_MIN;
-    const int32_t* const dl = delay + b;
-    const uint64_t* const w16 = (const uint64_t*)reqs + 2 * b + 1;   // pu_req16.b
-    const u64x2* const w32 = (const u64x2*)reqs + 2 * b + 1;         // the second half of a pu_req
 
-    for (uint64_t base = 0; base < len; base += (uint64_t)kThreads * kUnroll) {
+    // with the core id: out of range is counted without tables too
+    const RecordSource<FMT, true> src(reqs, delay, rg.b, len);
+    for (uint64_t base = 0; base < len; base += kTrip) {
         int32_t d[kUnroll];
-        u64x2 w[kUnroll];
+        typename RecordSource<FMT, true>::Word w[kUnroll];
         bool valid[kUnroll];
 #pragma unroll
-        for (int u = 0; u < kUnroll; u++) {
-            const uint64_t i = base + (uint64_t)(u * kThreads + tid);
-            valid[u] = i < len;
-            d[u] = 0;
-            w[u] = u64x2{0, 0};
-            if (valid[u]) {
-                d[u] = dl[i];
-                if (FMT == PU_REQ_FMT_16)
-                    w[u].x = w16[2 * i];
-                else
-                    w[u] = w32[2 * i];
-            }
-        }
+        for (int u = 0; u < kUnroll; u++) valid[u] = src.load(base + (uint64_t)(u * kThreads + tid), d[u], w[u]);
 #pragma unroll
         for (int u = 0; u < kUnroll; u++) {
             int32_t core;
@@ -283,13 +264,6 @@ int launch_reset(pu_dsum* s) {
     return s->record_after(s->stream, "pu_dsum_reset");
 }
 
-template <int FMT, bool CORES>
-void launch_add(pu_dsum* s, hipStream_t st, const void* d_reqs, const int32_t* d_delay, const uint64_t* d_begin,
-                const uint64_t* d_end) {
-    hipLaunchKernelGGL((dsum_add_kernel<FMT, CORES>), dim3((unsigned)s->count), dim3(kThreads), s->lds_bytes, st, s->rep,
-                       s->d_nc, s->d_core0, s->g_cnt, s->g_sum, d_reqs, d_delay, d_begin, d_end);
-}
-
 }  // namespace
 
 extern "C" {
@@ -352,31 +326,16 @@ void pu_dsum_close(pu_dsum* s) { pu::close_set(s); }
 
 int pu_dsum_add(pu_dsum* s, const void* d_reqs, int fmt, const int32_t* d_delay, const uint64_t* d_begin,
                 const uint64_t* d_end, void* hip_stream) {
-    if (!s || !pu::req_fmt_ok(fmt) || !d_reqs || !d_delay || !d_begin || !d_end || ((uintptr_t)d_reqs & 15))
-        return pu::set_error(PU_EINVAL, "pu_dsum_add: bad arguments");
-    int rc = s->use();
-    if (rc) return rc;
-    hipStream_t st = s->pick(hip_stream);
-    rc = s->order_before(st);
-    if (rc) return rc;
-    if (fmt == PU_REQ_FMT_16) {
-        if (s->cores)
-            launch_add<PU_REQ_FMT_16, true>(s, st, d_reqs, d_delay, d_begin, d_end);
-        else
-            launch_add<PU_REQ_FMT_16, false>(s, st, d_reqs, d_delay, d_begin, d_end);
-    } else {
-        if (s->cores)
-            launch_add<PU_REQ_FMT_32, true>(s, st, d_reqs, d_delay, d_begin, d_end);
-        else
-            launch_add<PU_REQ_FMT_32, false>(s, st, d_reqs, d_delay, d_begin, d_end);
-    }
-    return s->record_after(st, "pu_dsum_add");
+    return delay_add(s, "pu_dsum_add", d_reqs, fmt, d_delay, d_begin, d_end, hip_stream, [&](auto F, hipStream_t st) {
+        const auto kernel = s->cores ? dsum_add_kernel<decltype(F)::value, true> : dsum_add_kernel<decltype(F)::value, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)s->count), dim3(kThreads), s->lds_bytes, st, s->rep, s->d_nc, s->d_core0,
+                           s->g_cnt, s->g_sum, d_reqs, d_delay, d_begin, d_end);
+    });
 }
 
 int pu_dsum_read(pu_dsum* s, int first, int n, pu_dsum_replica* out) {
-    if (!s || first < 0 || n < 0 || (!out && n)) return pu::set_error(PU_EINVAL, "pu_dsum_read: bad arguments");
-    if ((int64_t)first + n > s->count) return pu::set_error(PU_ERANGE, "more replicas than the set holds");
-    if (n == 0) return 0;
+    const int rc = pu::replica_range(s ? s->count : 0, first, n, out != nullptr, "pu_dsum_read");
+    if (rc) return rc < 0 ? rc : 0;
     return s->read_back(
         [&](hipStream_t st) {
             return hipMemcpyAsync(out, s->rep + first, (size_t)n * sizeof(pu_dsum_replica), hipMemcpyDeviceToHost, st) ==
@@ -417,19 +376,9 @@ int pu_dsum_host_add(pu_dsum_replica* acc, uint64_t* core_count, int64_t* core_s
     if (!acc || !pu::req_fmt_ok(fmt) || (n && (!reqs || !delays)) || !core_count != !core_sum || (core_count && num_cores < 1))
         return pu::set_error(PU_EINVAL, "pu_dsum_host_add: bad arguments");
     const uint32_t limit = core_limit(num_cores);
-    const pu_req* r32 = (const pu_req*)reqs;
-    const pu_req16* r16 = (const pu_req16*)reqs;
     for (size_t i = 0; i < n; i++) {
-        int cls;
-        int32_t core;
-        if (fmt == PU_REQ_FMT_16) {
-            cls = class_of_req16_b(r16[i].b);
-            core = core_of_req16_b(r16[i].b);
-        } else {
-            cls = class_of_mem_type(r32[i].mem_type);
-            core = r32[i].core;
-        }
-        fold_one(&acc->cls[cls], delays[i]);
+        const int32_t core = pu_delay_record::core_at(reqs, fmt, i);
+        fold_one(&acc->cls[pu_delay_record::class_at(reqs, fmt, i)], delays[i]);
         if (core_out_of_range(core, limit)) {
             acc->core_out_of_range++;
         } else if (core_count) {

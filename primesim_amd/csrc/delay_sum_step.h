@@ -1,27 +1,25 @@
 // delay_sum_step.h — the rule of the delay summaries (pu_dsum_*,
 // include/primeuncore.h), shared by the host fold (pu_dsum_host_add) and the
-// device kernel (delay_sum.hip): a request's class, its core id, a delay's
-// bucket, and the fold of one (class, delay) pair into a summary.  Everything
-// here compiles as plain C++ on the host (PU_HD is empty there) and as
-// __host__ __device__ under hipcc's HIP mode.  All of it is integer and
-// independent of order, so any split of the work gives the same bits.
+// device kernel (delay_sum.hip): the range of core ids, a delay's bucket, and
+// the fold of one (class, delay) pair into a summary.  A record's class and core
+// id are delay_record_step.h's, named here too for whoever states the summaries'
+// rule whole.  Everything here compiles as plain C++ on the host (PU_HD is empty
+// there) and as __host__ __device__ under hipcc's HIP mode.  All of it is integer
+// and independent of order, so any split of the work gives the same bits.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
 
 #include "../../include/primeuncore.h"
+#include "delay_record_step.h"
 #include "pu_hd.h"
 
 namespace pu_delay_sum {
 
-// Class 0 is a read, class 1 a write.  The engine passes pu_req.mem_type on
-// unchanged as Req.type (engine.hip: replica_steps) and takes the write path
-// only where that equals PU_WR; PU_RD, PU_WB and every other value go the other
-// way.  pu_req16 carries one bit of it (PU_REQ16_TYPE).
-PU_HD inline int class_of_mem_type(uint32_t mem_type) { return mem_type == (uint32_t)PU_WR ? 1 : 0; }
-PU_HD inline int class_of_req16_b(uint64_t b) { return PU_REQ16_TYPE(b); }
-PU_HD inline int32_t core_of_req16_b(uint64_t b) { return PU_REQ16_CORE(b); }
+using pu_delay_record::class_of_mem_type;
+using pu_delay_record::class_of_req16_b;
+using pu_delay_record::core_of_req16_b;
 
 // Without a core count only a negative id is out of range.
 constexpr uint32_t kNoCoreLimit = 0x80000000u;

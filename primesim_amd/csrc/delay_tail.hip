@@ -15,9 +15,8 @@
 //
 // dtail_add_kernel<FMT>: one launch per call, one workgroup of 256 per replica,
 // which owns that replica's state for the launch; no atomics anywhere.
-//   * The loads are dhist_add_kernel's: lanes take consecutive records, four per lane
-//     and trip (a trip's loads are issued before any is used); of a pu_req16 only b,
-//     of a pu_req its last word (mem_type | ...), of the delays one dword.
+//   * The range and the loads are delay_stage.h's RecordSource, asked for the class
+//     alone: 8 B of a record.
 //   * Each wave keeps one sorted list per class in registers: lane j holds the j-th
 //     best (delay, index in the range) of the records the wave has met.  A record is
 //     a candidate while the wave's list is short, and once it holds k only when its
@@ -56,19 +55,15 @@
 
 #include "../../include/primeuncore.h"
 #include "common.h"
+#include "delay_stage.h"
 #include "delay_tail_step.h"
 #include "device_set.h"
 
 using namespace pu_delay_tail;
-using pu_delay_sum::class_of_mem_type;
-using pu_delay_sum::class_of_req16_b;
 using pu::round16;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kUnroll = 4;                 // records per lane and trip
 constexpr int kLists = kWaves + 1;         // the waves' lists and the stored one, per class
 constexpr int kStored = kWaves;            // the stored list's place among them
 constexpr int kMaxK = PU_DTAIL_MAX_K;
@@ -78,13 +73,6 @@ constexpr int kTotalThreads = 128;         // the total's workgroup: a wave per 
 
 static_assert(kMaxK == 64, "lane j of a wave holds a list's j-th entry");
 static_assert((1 << (kSearch - 1)) >= kMaxK, "the search reaches every entry");
-
-typedef unsigned long long u64;
-
-__global__ __launch_bounds__(kThreads) void dtail_reset_kernel(u64* state, size_t words) {
-    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i < words) state[i] = 0;
-}
 
 // The value of the lane below (lane 0 keeps its own): one DPP move, a wave shift right by one.
 __device__ inline int32_t from_lane_below(int32_t v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
@@ -137,16 +125,12 @@ __global__ __launch_bounds__(kThreads) void dtail_add_kernel(pu_dtail_entry* __r
     __shared__ pu_dtail_entry s_old[2][kMaxK];
 
     const int r = (int)blockIdx.x;
-    const uint64_t b = d_begin[r], e = d_end[r];
-    if (b >= e) return;   // the whole workgroup: nothing to add
-    const uint64_t len = e - b;
+    const RecordRange rg(d_begin, d_end);
+    if (rg.empty()) return;
+    const uint64_t len = rg.len();
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u64 seen = seen_of[r];
-
-    const int32_t* const dl = delay + b;
-    // the word that holds the class: pu_req16.b, or mem_type | ... of a pu_req (its last 8 bytes)
-    constexpr int kStride = FMT == PU_REQ_FMT_16 ? 2 : 4;
-    const uint64_t* const wd = (const uint64_t*)reqs + (uint64_t)kStride * b + (kStride - 1);
+    const RecordSource<FMT, false> src(reqs, delay, rg.b, len);
 
     // this wave's lists: (delay, index in the range) per class.  A stored list that is full bars
     // from the start: its entries are earlier than any record of this call, so a record whose
@@ -160,24 +144,15 @@ __global__ __launch_bounds__(kThreads) void dtail_add_kernel(pu_dtail_entry* __r
         }
     }
 
-    for (uint64_t base = 0; base < len; base += (uint64_t)kThreads * kUnroll) {
+    for (uint64_t base = 0; base < len; base += kTrip) {
         int32_t d[kUnroll];
         u64 w[kUnroll];
         bool valid[kUnroll];
 #pragma unroll
-        for (int u = 0; u < kUnroll; u++) {
-            const uint64_t i = base + (uint64_t)(u * kThreads + tid);
-            valid[u] = i < len;
-            d[u] = 0;
-            w[u] = 0;
-            if (valid[u]) {
-                d[u] = dl[i];
-                w[u] = wd[(uint64_t)kStride * i];
-            }
-        }
+        for (int u = 0; u < kUnroll; u++) valid[u] = src.load(base + (uint64_t)(u * kThreads + tid), d[u], w[u]);
 #pragma unroll
         for (int u = 0; u < kUnroll; u++) {
-            const int cls = FMT == PU_REQ_FMT_16 ? class_of_req16_b(w[u]) : class_of_mem_type((uint32_t)(w[u] & 0xFFu));
+            const int cls = src.cls(w[u]);
             const uint64_t first = base + (uint64_t)(u * kThreads + wave * 64);   // lane 0's record
 #pragma unroll
             for (int c = 0; c < 2; c++) {
@@ -240,7 +215,7 @@ __global__ __launch_bounds__(kThreads) void dtail_add_kernel(pu_dtail_entry* __r
         if (list == kStored) {
             *out = s_old[c][j];
         } else {   // new in this call: the request in full
-            const uint64_t i = b + (pv - seen);
+            const uint64_t i = rg.b + (pv - seen);
             *out = FMT == PU_REQ_FMT_16 ? entry_of(((const pu_req16*)reqs)[i], dv, pv) : entry_of(((const pu_req*)reqs)[i], dv, pv);
         }
     }
@@ -314,17 +289,6 @@ struct pu_dtail : pu::DeviceSet {
     uint32_t* tot_cnt = nullptr;
 };
 
-namespace {
-
-template <int FMT>
-void launch_add(pu_dtail* s, hipStream_t st, const void* d_reqs, const int32_t* d_delay, const uint64_t* d_begin,
-                const uint64_t* d_end) {
-    hipLaunchKernelGGL((dtail_add_kernel<FMT>), dim3((unsigned)s->count), dim3(kThreads), 0, st, s->entries, s->counts,
-                       s->seen, s->k, d_reqs, d_delay, d_begin, d_end);
-}
-
-}  // namespace
-
 extern "C" {
 
 pu_dtail* pu_dtail_open(int count, int k, int device) {
@@ -376,24 +340,15 @@ void pu_dtail_close(pu_dtail* s) { pu::close_set(s); }
 
 int pu_dtail_add(pu_dtail* s, const void* d_reqs, int fmt, const int32_t* d_delay, const uint64_t* d_begin,
                  const uint64_t* d_end, void* hip_stream) {
-    if (!s || !pu::req_fmt_ok(fmt) || !d_reqs || !d_delay || !d_begin || !d_end || ((uintptr_t)d_reqs & 15))
-        return pu::set_error(PU_EINVAL, "pu_dtail_add: bad arguments");
-    int rc = s->use();
-    if (rc) return rc;
-    hipStream_t st = s->pick(hip_stream);
-    rc = s->order_before(st);
-    if (rc) return rc;
-    if (fmt == PU_REQ_FMT_16)
-        launch_add<PU_REQ_FMT_16>(s, st, d_reqs, d_delay, d_begin, d_end);
-    else
-        launch_add<PU_REQ_FMT_32>(s, st, d_reqs, d_delay, d_begin, d_end);
-    return s->record_after(st, "pu_dtail_add");
+    return delay_add(s, "pu_dtail_add", d_reqs, fmt, d_delay, d_begin, d_end, hip_stream, [&](auto F, hipStream_t st) {
+        hipLaunchKernelGGL((dtail_add_kernel<decltype(F)::value>), dim3((unsigned)s->count), dim3(kThreads), 0, st, s->entries,
+                           s->counts, s->seen, s->k, d_reqs, d_delay, d_begin, d_end);
+    });
 }
 
 int pu_dtail_read(pu_dtail* s, int first, int n, pu_dtail_entry* out, uint32_t* count_out) {
-    if (!s || first < 0 || n < 0 || ((!out || !count_out) && n)) return pu::set_error(PU_EINVAL, "pu_dtail_read: bad arguments");
-    if ((int64_t)first + n > s->count) return pu::set_error(PU_ERANGE, "more replicas than the set holds");
-    if (n == 0) return 0;
+    const int rc = pu::replica_range(s ? s->count : 0, first, n, out && count_out, "pu_dtail_read");
+    if (rc) return rc < 0 ? rc : 0;
     const size_t list = (size_t)2 * s->k;
     return s->read_back(
         [&](hipStream_t st) {
@@ -406,17 +361,17 @@ int pu_dtail_read(pu_dtail* s, int first, int n, pu_dtail_entry* out, uint32_t* 
 }
 
 int pu_dtail_read_total(pu_dtail* s, int first, int n, pu_dtail_entry* out, int32_t* replica_out, uint32_t* count_out) {
-    if (!s || first < 0 || n < 0 || !out || !replica_out || !count_out)
-        return pu::set_error(PU_EINVAL, "pu_dtail_read_total: bad arguments");
-    if ((int64_t)first + n > s->count) return pu::set_error(PU_ERANGE, "more replicas than the set holds");
+    // n == 0 fills the outputs too: without them there is nothing to call, as without a set
+    int rc = pu::replica_range(s && out && replica_out && count_out ? s->count : 0, first, n, true, "pu_dtail_read_total");
+    if (rc < 0) return rc;
     const size_t list = (size_t)2 * s->k;
-    if (n == 0) {
+    if (rc) {
         std::memset(out, 0, list * sizeof(pu_dtail_entry));
         for (size_t i = 0; i < list; i++) replica_out[i] = -1;
         count_out[0] = count_out[1] = 0;
         return 0;
     }
-    int rc = s->use();
+    rc = s->use();
     if (rc) return rc;
     // on the set's own stream, after the set's last call by its event
     hipStream_t st = s->stream;
@@ -441,13 +396,7 @@ int pu_dtail_read_total(pu_dtail* s, int first, int n, pu_dtail_entry* out, int3
 
 int pu_dtail_reset(pu_dtail* s) {
     if (!s) return pu::set_error(PU_EINVAL, "pu_dtail_reset: no set");
-    int rc = s->use();
-    if (rc) return rc;
-    rc = s->order_before(s->stream);   // on the set's own stream, after the set's last call
-    if (rc) return rc;
-    hipLaunchKernelGGL(dtail_reset_kernel, dim3((unsigned)((s->reset_words + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                       s->stream, (u64*)s->base, s->reset_words);
-    return s->record_after(s->stream, "pu_dtail_reset");
+    return reset_words(s, s->base, s->reset_words, "pu_dtail_reset");
 }
 
 uint64_t pu_dtail_state_bytes(const pu_dtail* s) { return s ? (uint64_t)s->bytes : 0; }

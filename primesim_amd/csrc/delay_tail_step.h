@@ -1,21 +1,23 @@
 // delay_tail_step.h — the rule of the slowest-request lists (pu_dtail_*,
 // include/primeuncore.h), shared by the host fold (pu_dtail_host_add) and the
 // device kernels (delay_tail.hip): the order of two entries, a record as an entry,
-// and the sorted insertion that keeps a list of the best k.  A record's class is the
-// delay summaries' (pu_delay_sum::class_of_*).  Everything here compiles as plain
-// C++ on the host (PU_HD is empty there) and as __host__ __device__ under hipcc's
-// HIP mode.  All of it is integer, and a list is a function of the set of
-// (delay, position) pairs seen, so any split of the work gives the same bits.
+// and the sorted insertion that keeps a list of the best k.  A record's class is
+// delay_record_step.h's.  Everything here compiles as plain C++ on the host (PU_HD
+// is empty there) and as __host__ __device__ under hipcc's HIP mode.  All of it is
+// integer, and a list is a function of the set of (delay, position) pairs seen, so
+// any split of the work gives the same bits.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
 
 #include "../../include/primeuncore.h"
-#include "delay_sum_step.h"
+#include "delay_record_step.h"
 #include "pu_hd.h"
 
 namespace pu_delay_tail {
+
+using pu_delay_record::class_at;
 
 static_assert(sizeof(pu_dtail_entry) == 32, "three 8-byte and two 4-byte fields, no padding");
 
@@ -31,16 +33,12 @@ PU_HD inline pu_dtail_entry entry_of(const pu_req& q, int32_t delay, uint64_t po
     return pu_dtail_entry{q.addr, q.timer, position, delay, q.core};
 }
 PU_HD inline pu_dtail_entry entry_of(const pu_req16& q, int32_t delay, uint64_t position) {
-    return pu_dtail_entry{q.a, PU_REQ16_TIMER(q.b), position, delay, pu_delay_sum::core_of_req16_b(q.b)};
+    return pu_dtail_entry{q.a, PU_REQ16_TIMER(q.b), position, delay, pu_delay_record::core_of_req16_b(q.b)};
 }
 // record i of an array of pu_req (PU_REQ_FMT_32) or pu_req16 (PU_REQ_FMT_16)
 PU_HD inline pu_dtail_entry entry_at(const void* reqs, int fmt, size_t i, int32_t delay, uint64_t position) {
     return fmt == PU_REQ_FMT_16 ? entry_of(((const pu_req16*)reqs)[i], delay, position)
                                 : entry_of(((const pu_req*)reqs)[i], delay, position);
-}
-PU_HD inline int class_at(const void* reqs, int fmt, size_t i) {
-    return fmt == PU_REQ_FMT_16 ? pu_delay_sum::class_of_req16_b(((const pu_req16*)reqs)[i].b)
-                                : pu_delay_sum::class_of_mem_type(((const pu_req*)reqs)[i].mem_type);
 }
 
 // The number of the list's entries (best first, `count` of them) that are better than (delay, position).

@@ -10,6 +10,10 @@
 // `ev`.  Calls that stay on one stream are ordered by the stream and wait for
 // nothing.  Reading back and closing wait for `ev` on the host, so only for the
 // set's own work.
+//
+// replica_range is the readers' check of first and n against the set.  What the three
+// delay stages share beyond that, the record reader of their kernels and delay_add
+// around their launches, is in delay_stage.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -24,6 +28,15 @@
 namespace pu {
 
 inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// The first / n / out check of a reader `who` ("pu_x_read") of replicas [first, first + n)
+// of a set that holds set_count (0: there is no set); have_out: the output is there, which
+// only n > 0 needs.  1: nothing to do (n == 0), 0: go on, else PU_E* with the error text.
+inline int replica_range(int set_count, int first, int n, bool have_out, const char* who) {
+    if (set_count < 1 || first < 0 || n < 0 || (!have_out && n)) return set_error(PU_EINVAL, std::string(who) + ": bad arguments");
+    if ((int64_t)first + n > set_count) return set_error(PU_ERANGE, "more replicas than the set holds");
+    return n == 0 ? 1 : 0;
+}
 
 struct DeviceSet {
     int device = 0;

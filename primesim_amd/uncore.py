@@ -246,6 +246,36 @@ def _state_bytes(entry: str, doc: str) -> property:
     return property(lambda self: int(getattr(lib(), entry)(self._handle())), doc=doc)
 
 
+class _DelayStage(_Owner):
+    """What the three delay stages share: `_n` replicas, and the entries `<_entry>_add`,
+    `<_entry>_reset` and the readers, called on the handle by `_call`."""
+    _entry = ""
+    _n = 0
+
+    def _call(self, name: str, *args) -> None:
+        rc = getattr(lib(), f"{self._entry}_{name}")(self._handle(), *args)
+        if rc != 0:
+            raise UncoreError(f"{self._entry}_{name}: {last_error()} ({rc})")
+
+    def _count(self, first: int, n: Optional[int]) -> int:
+        """n of a reader's (first, n): by default the replicas from first on."""
+        return self._n - first if n is None else n
+
+    def __len__(self) -> int:
+        return self._n
+
+    def add(self, d_reqs_ptr: int, d_delay_ptr: int, d_begin_ptr: int, d_end_ptr: int, fmt: int = A.PU_REQ_FMT_32,
+            stream_ptr: int = 0) -> None:
+        """Asynchronous on stream_ptr (a hipStream_t as an integer); 0 is the set's own
+        stream, which is not ordered with torch's streams.  d_begin / d_end: device uint64,
+        one entry per replica, in records (d_off and d_off + 1 after run_device)."""
+        self._call("add", d_reqs_ptr or None, fmt, d_delay_ptr or None, d_begin_ptr or None, d_end_ptr or None,
+                   stream_ptr or None)
+
+    def reset(self) -> None:
+        self._call("reset")
+
+
 # PU_E* codes (include/primeuncore.h).  pu_access returns them in-band (a
 # wrapped delay may collide with one); the mirror uses pu_access_status.
 PU_ERRORS = (-5, -12, -19, -22, -34, -71, -95)
@@ -630,13 +660,13 @@ def summarize_delays(reqs: np.ndarray, delays: np.ndarray, num_cores: Optional[i
     return out[0], cnt, sm
 
 
-class DeviceDelaySummary(_Owner):
+class DeviceDelaySummary(_DelayStage):
     """Per-replica delay summaries kept on the device (pu_dsum_*): `add` folds every
     replica's records [begin[r], end[r]) of device request and delay arrays into its
     running summary, bit for bit what summarize_delays gives.  num_cores (one entry per
     replica) adds per-core (count, sum) tables.  Pointers are plain integers
     (tensor.data_ptr()).  Needs a GPU: there is no host fallback."""
-    _close, _no_handle = "pu_dsum_close", "DeviceDelaySummary is closed"
+    _entry, _close, _no_handle = "pu_dsum", "pu_dsum_close", "DeviceDelaySummary is closed"
 
     def __init__(self, count: int, num_cores=None, device: int = 0):
         self._n = count
@@ -652,43 +682,21 @@ class DeviceDelaySummary(_Owner):
             raise UncoreError(f"pu_dsum_open: {last_error()}")
         self._h = h
 
-    def __len__(self) -> int:
-        return self._n
-
     state_bytes = _state_bytes("pu_dsum_state_bytes", "Device memory the set holds.")
-
-    def add(self, d_reqs_ptr: int, d_delay_ptr: int, d_begin_ptr: int, d_end_ptr: int, fmt: int = A.PU_REQ_FMT_32,
-            stream_ptr: int = 0) -> None:
-        """Asynchronous on stream_ptr (a hipStream_t as an integer); 0 is the set's own
-        stream, which is not ordered with torch's streams.  d_begin / d_end: device uint64,
-        one entry per replica, in records (d_off and d_off + 1 after run_device)."""
-        rc = lib().pu_dsum_add(self._handle(), d_reqs_ptr or None, fmt, d_delay_ptr or None, d_begin_ptr or None,
-                               d_end_ptr or None, stream_ptr or None)
-        if rc != 0:
-            raise UncoreError(f"pu_dsum_add: {last_error()} ({rc})")
 
     def read(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """Summaries of replicas [first, first + n) as A.DSUM_DTYPE records (waits for the set's calls)."""
-        n = self._n - first if n is None else n
+        n = self._count(first, n)
         out = np.zeros(max(n, 0), dtype=A.DSUM_DTYPE)
-        rc = lib().pu_dsum_read(self._handle(), first, n, _as(out, A.DsumReplica))
-        if rc != 0:
-            raise UncoreError(f"pu_dsum_read: {last_error()} ({rc})")
+        self._call("read", first, n, _as(out, A.DsumReplica))
         return out
 
     def cores(self, replica: int) -> tuple[np.ndarray, np.ndarray]:
         """(count, sum) per core of one replica; raises for a set opened without num_cores."""
         nc = self._nc[replica] if self._nc is not None and 0 <= replica < self._n else 0
         cnt, sm = np.zeros(nc, dtype=np.uint64), np.zeros(nc, dtype=np.int64)
-        rc = lib().pu_dsum_read_cores(self._handle(), replica, _as(cnt, C.c_uint64), _as(sm, C.c_int64), nc)
-        if rc != 0:
-            raise UncoreError(f"pu_dsum_read_cores: {last_error()} ({rc})")
+        self._call("read_cores", replica, _as(cnt, C.c_uint64), _as(sm, C.c_int64), nc)
         return cnt, sm
-
-    def reset(self) -> None:
-        rc = lib().pu_dsum_reset(self._handle())
-        if rc != 0:
-            raise UncoreError(f"pu_dsum_reset: {last_error()} ({rc})")
 
 
 # ---------------------------------------------------------------- delay histograms
@@ -751,13 +759,13 @@ def histogram_quantiles(hist: np.ndarray, ppm) -> tuple[np.ndarray, np.ndarray]:
     return count.reshape(h.shape[:-1]), bucket.reshape(h.shape[:-1] + (bucket.shape[1],))
 
 
-class DeviceDelayHistogram(_Owner):
+class DeviceDelayHistogram(_DelayStage):
     """Per-replica log-linear delay histograms kept on the device (pu_dhist_*): `add` counts
     every replica's records [begin[r], end[r]) of device request and delay arrays into its
     [2, PU_DHIST_BUCKETS] histogram, bit for bit what delay_histogram gives; `quantiles`
     and `total` are formed on the device.  Pointers are plain integers (tensor.data_ptr()).
     Needs a GPU: there is no host fallback."""
-    _close, _no_handle = "pu_dhist_close", "DeviceDelayHistogram is closed"
+    _entry, _close, _no_handle = "pu_dhist", "pu_dhist_close", "DeviceDelayHistogram is closed"
 
     def __init__(self, count: int, device: int = 0):
         self._n = count
@@ -766,55 +774,31 @@ class DeviceDelayHistogram(_Owner):
             raise UncoreError(f"pu_dhist_open: {last_error()}")
         self._h = h
 
-    def __len__(self) -> int:
-        return self._n
-
     state_bytes = _state_bytes("pu_dhist_state_bytes", "Device memory the set holds.")
-
-    def add(self, d_reqs_ptr: int, d_delay_ptr: int, d_begin_ptr: int, d_end_ptr: int, fmt: int = A.PU_REQ_FMT_32,
-            stream_ptr: int = 0) -> None:
-        """As DeviceDelaySummary.add: asynchronous on stream_ptr (0 is the set's own stream);
-        d_begin / d_end: device uint64, one entry per replica, in records."""
-        rc = lib().pu_dhist_add(self._handle(), d_reqs_ptr or None, fmt, d_delay_ptr or None, d_begin_ptr or None,
-                                d_end_ptr or None, stream_ptr or None)
-        if rc != 0:
-            raise UncoreError(f"pu_dhist_add: {last_error()} ({rc})")
 
     def read(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """Histograms of replicas [first, first + n): uint64 [n, 2, PU_DHIST_BUCKETS] (waits for the set's calls)."""
-        n = self._n - first if n is None else n
+        n = self._count(first, n)
         out = np.zeros((max(n, 0), 2, A.PU_DHIST_BUCKETS), dtype=np.uint64)
-        rc = lib().pu_dhist_read(self._handle(), first, n, _as(out, C.c_uint64))
-        if rc != 0:
-            raise UncoreError(f"pu_dhist_read: {last_error()} ({rc})")
+        self._call("read", first, n, _as(out, C.c_uint64))
         return out
 
     def quantiles(self, ppm, first: int = 0, n: Optional[int] = None) -> tuple[np.ndarray, np.ndarray]:
         """(count, bucket) of replicas [first, first + n), formed on the device: count uint64 [n, 2],
         bucket int32 [n, 2, len(ppm)] (-1 for an empty class); ppm: up to PU_DHIST_MAX_Q quantiles
         in parts per million.  dhist_bucket_bounds gives the delays a bucket holds."""
-        n = self._n - first if n is None else n
+        n = self._count(first, n)
         q = _ppm_array(ppm)
         out = np.zeros((max(n, 0), 2), dtype=A.DHIST_Q_DTYPE)
-        rc = lib().pu_dhist_quantiles(self._handle(), first, n, _as(q, C.c_uint32), len(q), _as(out, A.DhistQuantile))
-        if rc != 0:
-            raise UncoreError(f"pu_dhist_quantiles: {last_error()} ({rc})")
+        self._call("quantiles", first, n, _as(q, C.c_uint32), len(q), _as(out, A.DhistQuantile))
         return out["count"].copy(), out["bucket"][:, :, :len(q)].copy()
 
     def total(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """The histogram summed over replicas [first, first + n): uint64 [2, PU_DHIST_BUCKETS].
         Histograms add elementwise, so ranks sum what this returns."""
-        n = self._n - first if n is None else n
         out = np.zeros((2, A.PU_DHIST_BUCKETS), dtype=np.uint64)
-        rc = lib().pu_dhist_read_total(self._handle(), first, n, _as(out, C.c_uint64))
-        if rc != 0:
-            raise UncoreError(f"pu_dhist_read_total: {last_error()} ({rc})")
+        self._call("read_total", first, self._count(first, n), _as(out, C.c_uint64))
         return out
-
-    def reset(self) -> None:
-        rc = lib().pu_dhist_reset(self._handle())
-        if rc != 0:
-            raise UncoreError(f"pu_dhist_reset: {last_error()} ({rc})")
 
 
 # ---------------------------------------------------------------- slowest requests
@@ -846,13 +830,13 @@ def delay_tail(reqs: np.ndarray, delays: np.ndarray, k: int, fmt: int = A.PU_REQ
     return entries, counts, int(seen.value)
 
 
-class DeviceDelayTail(_Owner):
+class DeviceDelayTail(_DelayStage):
     """Per-replica lists of the k slowest reads and the k slowest writes kept on the device
     (pu_dtail_*): `add` offers every replica's records [begin[r], end[r]) of device request and
     delay arrays to its lists, bit for bit what delay_tail gives; `total` is the best k of the
     ensemble, formed on the device.  Pointers are plain integers (tensor.data_ptr()).
     Needs a GPU: there is no host fallback."""
-    _close, _no_handle = "pu_dtail_close", "DeviceDelayTail is closed"
+    _entry, _close, _no_handle = "pu_dtail", "pu_dtail_close", "DeviceDelayTail is closed"
 
     def __init__(self, count: int, k: int = 16, device: int = 0):
         self._n, self._k = count, k
@@ -861,9 +845,6 @@ class DeviceDelayTail(_Owner):
             raise UncoreError(f"pu_dtail_open: {last_error()}")
         self._h = h
 
-    def __len__(self) -> int:
-        return self._n
-
     @property
     def k(self) -> int:
         """Entries a list holds at most."""
@@ -871,46 +852,25 @@ class DeviceDelayTail(_Owner):
 
     state_bytes = _state_bytes("pu_dtail_state_bytes", "Device memory the set holds.")
 
-    def add(self, d_reqs_ptr: int, d_delay_ptr: int, d_begin_ptr: int, d_end_ptr: int, fmt: int = A.PU_REQ_FMT_32,
-            stream_ptr: int = 0) -> None:
-        """As DeviceDelaySummary.add: asynchronous on stream_ptr (0 is the set's own stream);
-        d_begin / d_end: device uint64, one entry per replica, in records."""
-        rc = lib().pu_dtail_add(self._handle(), d_reqs_ptr or None, fmt, d_delay_ptr or None, d_begin_ptr or None,
-                                d_end_ptr or None, stream_ptr or None)
-        if rc != 0:
-            raise UncoreError(f"pu_dtail_add: {last_error()} ({rc})")
-
     def read(self, first: int = 0, n: Optional[int] = None) -> tuple[np.ndarray, np.ndarray]:
         """(entries, counts) of replicas [first, first + n): A.DTAIL_DTYPE [n, 2, k], best first and zero
         past the count, and uint32 [n, 2] (waits for the set's calls)."""
-        h = self._handle()
-        n = self._n - first if n is None else n
+        n = self._count(first, n)
         entries = np.zeros((max(n, 0), 2, self._k), dtype=A.DTAIL_DTYPE)
         counts = np.zeros((max(n, 0), 2), dtype=np.uint32)
-        rc = lib().pu_dtail_read(h, first, n, _as(entries, A.DtailEntry), _as(counts, C.c_uint32))
-        if rc != 0:
-            raise UncoreError(f"pu_dtail_read: {last_error()} ({rc})")
+        self._call("read", first, n, _as(entries, A.DtailEntry), _as(counts, C.c_uint32))
         return entries, counts
 
     def total(self, first: int = 0, n: Optional[int] = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(entries, replicas, counts) of the best k over replicas [first, first + n), per class:
         A.DTAIL_DTYPE [2, k], int32 [2, k] (-1 past the count) and uint32 [2]; by delay descending,
         then replica, then position.  Lists of different ranks merge by the same order on the host."""
-        h = self._handle()
-        n = self._n - first if n is None else n
         entries = np.zeros((2, self._k), dtype=A.DTAIL_DTYPE)
         replicas = np.full((2, self._k), -1, dtype=np.int32)
         counts = np.zeros(2, dtype=np.uint32)
-        rc = lib().pu_dtail_read_total(h, first, n, _as(entries, A.DtailEntry), _as(replicas, C.c_int32),
-                                       _as(counts, C.c_uint32))
-        if rc != 0:
-            raise UncoreError(f"pu_dtail_read_total: {last_error()} ({rc})")
+        self._call("read_total", first, self._count(first, n), _as(entries, A.DtailEntry), _as(replicas, C.c_int32),
+                   _as(counts, C.c_uint32))
         return entries, replicas, counts
-
-    def reset(self) -> None:
-        rc = lib().pu_dtail_reset(self._handle())
-        if rc != 0:
-            raise UncoreError(f"pu_dtail_reset: {last_error()} ({rc})")
 
 
 QUEUE_KINDS = ("x", "y", "z", "bus")     # pu_config_queue_ends: kind 0 .. 3

@@ -12,12 +12,9 @@ the device.  The kernels' marks: a wave is 64 records, a workgroup pass 256, a t
 the loop 1,024; a lane of the quantile scan takes 14 buckets; the total's first pass
 has at most 120 replica groups.
 """
-import contextlib
 import ctypes as C
-import functools
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -27,51 +24,23 @@ import primesim_amd as P
 from primesim_amd import _abi as A
 from primesim_amd import config as CF
 from primesim_amd import uncore as U
+from delay_stage_util import FMTS, LENGTHS, REC, ROOT, data, opened, run_golden, summary_tool
+from delay_stage_util import add as _add, idx as _idx, to_dev as _to_dev
 from dhist_fold import EDGE_DELAYS_FINE, NB, buckets, coarse, fold, quantile_buckets, sorted_quantile
 from dsum_fold import I32_MAX, I32_MIN, synth
 from golden_util import Case
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FMTS = [A.PU_REQ_FMT_32, A.PU_REQ_FMT_16]
-REC = {A.PU_REQ_FMT_32: 32, A.PU_REQ_FMT_16: 16}
 PPMS = [0, 1, 500000, 900000, 990000, 999000, 999999, 1000000]
 
 
-@contextlib.contextmanager
 def _open(count):
-    ds = P.DeviceDelayHistogram(count)
-    try:
-        yield ds
-    finally:
-        ds.close()
+    return opened(P.DeviceDelayHistogram, count)
 
 
-def _to_dev(reqs, delays, fmt):
-    """(request records, delays) as device tensors; the copies are done when this returns."""
-    import torch
-    host = np.ascontiguousarray(reqs) if fmt == A.PU_REQ_FMT_32 else U.pack_req16(np.ascontiguousarray(reqs))
-    b = host.view(np.uint8).reshape(len(reqs), REC[fmt]).copy()
-    d_reqs = torch.from_numpy(b).to("cuda:0")
-    d_del = torch.from_numpy(np.ascontiguousarray(delays, dtype=np.int32).copy()).to("cuda:0")
-    torch.cuda.synchronize()
-    return d_reqs, d_del
-
-
-def _idx(values):
-    import torch
-    t = torch.tensor([int(v) for v in values], dtype=torch.int64, device="cuda:0")
-    torch.cuda.synchronize()
-    return t
-
-
-def _add(ds, dev, begins, ends, fmt, stream=None):
-    """One add of ranges [begins[r], ends[r]); returns the index tensors (alive until the caller has read)."""
-    b, e = _idx(begins), _idx(ends)
-    ds.add(dev[0].data_ptr(), dev[1].data_ptr(), b.data_ptr(), e.data_ptr(), fmt=fmt,
-           stream_ptr=stream.cuda_stream if stream is not None else 0)
-    return b, e
+def _data(n, seed):
+    return data(n, 70, seed)
 
 
 def _want(acc, reqs, delays, b, e):
@@ -89,14 +58,6 @@ def _verify(ds, wants, what):
     return got
 
 
-@functools.lru_cache(maxsize=None)
-def _data(n, seed):
-    r, d = synth(n, 70, seed)
-    r.setflags(write=False)
-    d.setflags(write=False)
-    return r, d
-
-
 # ---------------------------------------------------------------- ranges
 @pytest.mark.parametrize("begin", [0, 1, 3, 5])
 @pytest.mark.parametrize("fmt", FMTS)
@@ -105,7 +66,7 @@ def test_one_replica_any_length_and_alignment(fmt, begin):
     reqs, delays = _data(1100, 21)
     dev = _to_dev(reqs, delays, fmt)
     with _open(1) as ds:
-        for n in (0, 1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025):
+        for n in LENGTHS:
             ds.reset()
             keep = _add(ds, dev, [begin], [begin + n], fmt)
             got = _verify(ds, [_want(None, reqs, delays, begin, begin + n)], f"begin {begin}, {n} records")
@@ -393,33 +354,8 @@ def test_ensemble_total_over_more_than_one_replica_group(fmt):
 # ---------------------------------------------------------------- with the engine
 def _run_and_count(c, d_reqs, fmt, s):
     """The golden's requests (already on the device) through run_device and DeviceDelayHistogram on stream s."""
-    import torch
-    n = len(c.reqs)
-    um = P.UncoreManager()
-    um.init(P.load_config(c.xml_path), replicas=1)
-    ds = P.DeviceDelayHistogram(1)
-    try:
-        if c.closed:
-            um.set_replay_mode(U.PU_REPLAY_CLOSED)
-        for prog, th in c.threads:
-            um.allocCore(prog, th)
-        d_off = torch.tensor([0, n], dtype=torch.int64, device="cuda:0")
-        d_del = torch.full((n,), -7, dtype=torch.int32, device="cuda:0")
-        um.set_device_req_format(fmt)
-        try:
-            torch.cuda.synchronize()
-            um.run_device(d_reqs.data_ptr(), d_off.data_ptr(), d_del.data_ptr(), s.cuda_stream)
-            ds.add(d_reqs.data_ptr(), d_del.data_ptr(), d_off.data_ptr(), d_off.data_ptr() + 8, fmt=fmt,
-                   stream_ptr=s.cuda_stream)
-            got = ds.read()[0]
-            _, bucket = ds.quantiles([500000, 990000, 999000])
-            s.synchronize()
-        finally:
-            um.set_device_req_format(A.PU_REQ_FMT_32)
-        c.check_delays(d_del.cpu().numpy())
-    finally:
-        ds.close()
-        um.close()
+    got, (_, bucket) = run_golden(c, d_reqs, fmt, s, lambda: P.DeviceDelayHistogram(1),
+                                  lambda ds: (ds.read()[0], ds.quantiles([500000, 990000, 999000])))
     reqs, delays = np.ascontiguousarray(c.reqs), np.ascontiguousarray(c.delays)
     np.testing.assert_array_equal(got, P.delay_histogram(reqs, delays), err_msg=f"{c.name}: device vs delay_histogram")
     np.testing.assert_array_equal(got, fold(reqs, delays), err_msg=f"{c.name}: device vs numpy")
@@ -470,11 +406,7 @@ def test_ensemble_summary_tool_with_quantiles():
     quantile objects equal those of the host functions over a StreamSet -> run_device run of the same seeds."""
     import torch
     R, n, chunks, base, nc = 4, 2000, 2, 500, 16
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "ensemble_summary.py"), "--preset", "C1", "--kind", "1",
-                        "--replicas", str(R), "--chunk", str(n), "--chunks", str(chunks), "--seed-base", str(base),
-                        "--quantiles"], capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0, r.stdout + r.stderr
-    lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    lines = [json.loads(x) for x in summary_tool("--seed-base", str(base), "--quantiles")]
     assert len(lines) == R + 1 and [x["replica"] for x in lines[:R]] == list(range(R))
 
     cfg = P.config_from_dict(CF.preset("C1"))

@@ -9,10 +9,8 @@ The kernel needs no engine: requests and delays are synthetic numpy arrays copie
 to the device.  The kernel's marks: a wave is 64 records, a workgroup pass 256, a
 trip of the loop 1,024; per-core tables are in LDS up to 1,024 cores.
 """
-import functools
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -21,42 +19,14 @@ import pytest
 import primesim_amd as P
 from primesim_amd import _abi as A
 from primesim_amd import config as CF
-from primesim_amd import uncore as U
+from delay_stage_util import FMTS, LENGTHS, REC, ROOT, run_golden, summary_tool
+from delay_stage_util import add as _add, data as _data, idx as _idx, to_dev as _to_dev
 from dsum_fold import EDGE_DELAYS, I32_MAX, I32_MIN, assert_same, fold, synth
 from golden_util import Case
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FMTS = [A.PU_REQ_FMT_32, A.PU_REQ_FMT_16]
-REC = {A.PU_REQ_FMT_32: 32, A.PU_REQ_FMT_16: 16}
 LDS_CORES = 1024       # delay_sum.hip: kLdsCores
-
-
-def _to_dev(reqs, delays, fmt):
-    """(request records, delays) as device tensors; the copies are done when this returns."""
-    import torch
-    host = np.ascontiguousarray(reqs) if fmt == A.PU_REQ_FMT_32 else U.pack_req16(np.ascontiguousarray(reqs))
-    b = host.view(np.uint8).reshape(len(reqs), REC[fmt]).copy()
-    d_reqs = torch.from_numpy(b).to("cuda:0")
-    d_del = torch.from_numpy(np.ascontiguousarray(delays, dtype=np.int32).copy()).to("cuda:0")
-    torch.cuda.synchronize()
-    return d_reqs, d_del
-
-
-def _idx(values):
-    import torch
-    t = torch.tensor([int(v) for v in values], dtype=torch.int64, device="cuda:0")
-    torch.cuda.synchronize()
-    return t
-
-
-def _add(ds, dev, begins, ends, fmt, stream=None):
-    """One add of ranges [begins[r], ends[r]); returns the index tensors (alive until the caller has read)."""
-    b, e = _idx(begins), _idx(ends)
-    ds.add(dev[0].data_ptr(), dev[1].data_ptr(), b.data_ptr(), e.data_ptr(), fmt=fmt,
-           stream_ptr=stream.cuda_stream if stream is not None else 0)
-    return b, e
 
 
 def _empty(nc):
@@ -81,14 +51,6 @@ def _verify(ds, wants, what, tables=True):
             np.testing.assert_array_equal(sm, w[2], err_msg=f"{what}: replica {r} per-core sum")
 
 
-@functools.lru_cache(maxsize=None)
-def _data(n, nc, seed):
-    r, d = synth(n, nc, seed)
-    r.setflags(write=False)
-    d.setflags(write=False)
-    return r, d
-
-
 # ---------------------------------------------------------------- ranges
 @pytest.mark.parametrize("begin", [0, 1, 3, 5])
 @pytest.mark.parametrize("fmt", FMTS)
@@ -99,7 +61,7 @@ def test_one_replica_any_length_and_alignment(fmt, begin):
     dev = _to_dev(reqs, delays, fmt)
     ds = P.DeviceDelaySummary(1, num_cores=[nc])
     try:
-        for n in (0, 1, 63, 64, 65, 255, 256, 257, 1000, 1023, 1024, 1025):
+        for n in sorted(LENGTHS + (1000,)):
             ds.reset()
             keep = _add(ds, dev, [begin], [begin + n], fmt)
             _verify(ds, [_want(None, reqs, delays, begin, begin + n, nc)], f"begin {begin}, {n} records")
@@ -371,33 +333,9 @@ def test_add_and_read_validate_their_arguments():
 # ---------------------------------------------------------------- with the engine
 def _run_and_summarise(c, d_reqs, fmt, s):
     """The golden's requests (already on the device) through run_device and DeviceDelaySummary on stream s."""
-    import torch
-    n, nc = len(c.reqs), len(c.completion)
-    um = P.UncoreManager()
-    um.init(P.load_config(c.xml_path), replicas=1)
-    ds = P.DeviceDelaySummary(1, num_cores=[nc])
-    try:
-        if c.closed:
-            um.set_replay_mode(U.PU_REPLAY_CLOSED)
-        for prog, th in c.threads:
-            um.allocCore(prog, th)
-        d_off = torch.tensor([0, n], dtype=torch.int64, device="cuda:0")
-        d_del = torch.full((n,), -7, dtype=torch.int32, device="cuda:0")
-        um.set_device_req_format(fmt)
-        try:
-            torch.cuda.synchronize()
-            um.run_device(d_reqs.data_ptr(), d_off.data_ptr(), d_del.data_ptr(), s.cuda_stream)
-            ds.add(d_reqs.data_ptr(), d_del.data_ptr(), d_off.data_ptr(), d_off.data_ptr() + 8, fmt=fmt,
-                   stream_ptr=s.cuda_stream)
-            got = ds.read()[0]
-            cnt, sm = ds.cores(0)
-            s.synchronize()
-        finally:
-            um.set_device_req_format(A.PU_REQ_FMT_32)
-        c.check_delays(d_del.cpu().numpy())
-    finally:
-        ds.close()
-        um.close()
+    nc = len(c.completion)
+    got, (cnt, sm) = run_golden(c, d_reqs, fmt, s, lambda: P.DeviceDelaySummary(1, num_cores=[nc]),
+                                lambda ds: (ds.read()[0], ds.cores(0)))
     want = fold(np.ascontiguousarray(c.reqs), np.ascontiguousarray(c.delays), num_cores=nc)
     assert_same(got, want[0], c.name)
     np.testing.assert_array_equal(cnt, want[1])
@@ -442,11 +380,7 @@ def test_ensemble_summary_tool():
     equal summarize_delays over a StreamSet -> run_device run of the same seeds."""
     import torch
     R, n, chunks, base, nc = 4, 2000, 2, 500, 16
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "ensemble_summary.py"), "--preset", "C1", "--kind", "1",
-                        "--replicas", str(R), "--chunk", str(n), "--chunks", str(chunks), "--seed-base", str(base)],
-                       capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0, r.stdout + r.stderr
-    lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    lines = [json.loads(x) for x in summary_tool("--seed-base", str(base))]
     assert [x["replica"] for x in lines] == list(range(R))
 
     cfg = P.config_from_dict(CF.preset("C1"))

@@ -10,12 +10,9 @@ The kernels need no engine: requests and delays are synthetic numpy arrays copie
 device.  The kernels' marks: a wave is 64 records, a workgroup pass 256, a trip of the loop
 1,024; a list has 1, 5 or 64 entries; the total's first pass has at most 120 replica groups.
 """
-import contextlib
 import ctypes as C
-import functools
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -25,50 +22,21 @@ import primesim_amd as P
 from primesim_amd import _abi as A
 from primesim_amd import config as CF
 from primesim_amd import uncore as U
+from delay_stage_util import FMTS, LENGTHS, REC, ROOT, data, opened, run_golden
+from delay_stage_util import add as _add, idx as _idx, summary_tool as _tool, to_dev as _to_dev
 from dsum_fold import I32_MAX, synth
 from dtail_fold import assert_same, fold, total
 from golden_util import Case
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FMTS = [A.PU_REQ_FMT_32, A.PU_REQ_FMT_16]
-REC = {A.PU_REQ_FMT_32: 32, A.PU_REQ_FMT_16: 16}
 
-
-@contextlib.contextmanager
 def _open(count, k):
-    ds = P.DeviceDelayTail(count, k)
-    try:
-        yield ds
-    finally:
-        ds.close()
+    return opened(P.DeviceDelayTail, count, k)
 
 
-def _to_dev(reqs, delays, fmt):
-    """(request records, delays) as device tensors; the copies are done when this returns."""
-    import torch
-    host = np.ascontiguousarray(reqs) if fmt == A.PU_REQ_FMT_32 else U.pack_req16(np.ascontiguousarray(reqs))
-    b = host.view(np.uint8).reshape(len(reqs), REC[fmt]).copy()
-    d_reqs = torch.from_numpy(b).to("cuda:0")
-    d_del = torch.from_numpy(np.ascontiguousarray(delays, dtype=np.int32).copy()).to("cuda:0")
-    torch.cuda.synchronize()
-    return d_reqs, d_del
-
-
-def _idx(values):
-    import torch
-    t = torch.tensor([int(v) for v in values], dtype=torch.int64, device="cuda:0")
-    torch.cuda.synchronize()
-    return t
-
-
-def _add(ds, dev, begins, ends, fmt, stream=None):
-    """One add of ranges [begins[r], ends[r]); returns the index tensors (alive until the caller has read)."""
-    b, e = _idx(begins), _idx(ends)
-    ds.add(dev[0].data_ptr(), dev[1].data_ptr(), b.data_ptr(), e.data_ptr(), fmt=fmt,
-           stream_ptr=stream.cuda_stream if stream is not None else 0)
-    return b, e
+def _data(n, seed):
+    return data(n, 70, seed)
 
 
 def _want(acc, reqs, delays, k, b, e):
@@ -87,17 +55,6 @@ def _verify(ds, wants, what):
         for c in (0, 1):
             assert not entries[r][c][int(counts[r][c]):].view(np.uint8).any(), f"{what}: replica {r} past the count"
     return entries, counts
-
-
-@functools.lru_cache(maxsize=None)
-def _data(n, seed):
-    r, d = synth(n, 70, seed)
-    r.setflags(write=False)
-    d.setflags(write=False)
-    return r, d
-
-
-LENGTHS = (0, 1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025)
 
 
 # ---------------------------------------------------------------- ranges
@@ -381,32 +338,7 @@ def test_ensemble_total_over_more_than_one_replica_group(fmt, k):
 # ---------------------------------------------------------------- with the engine
 def _run_and_list(c, d_reqs, fmt, s, k=16):
     """The golden's requests (already on the device) through run_device and DeviceDelayTail on stream s."""
-    import torch
-    n = len(c.reqs)
-    um = P.UncoreManager()
-    um.init(P.load_config(c.xml_path), replicas=1)
-    ds = P.DeviceDelayTail(1, k)
-    try:
-        if c.closed:
-            um.set_replay_mode(U.PU_REPLAY_CLOSED)
-        for prog, th in c.threads:
-            um.allocCore(prog, th)
-        d_off = torch.tensor([0, n], dtype=torch.int64, device="cuda:0")
-        d_del = torch.full((n,), -7, dtype=torch.int32, device="cuda:0")
-        um.set_device_req_format(fmt)
-        try:
-            torch.cuda.synchronize()
-            um.run_device(d_reqs.data_ptr(), d_off.data_ptr(), d_del.data_ptr(), s.cuda_stream)
-            ds.add(d_reqs.data_ptr(), d_del.data_ptr(), d_off.data_ptr(), d_off.data_ptr() + 8, fmt=fmt,
-                   stream_ptr=s.cuda_stream)
-            ent, cnt = ds.read()
-            s.synchronize()
-        finally:
-            um.set_device_req_format(A.PU_REQ_FMT_32)
-        c.check_delays(d_del.cpu().numpy())
-    finally:
-        ds.close()
-        um.close()
+    ent, cnt = run_golden(c, d_reqs, fmt, s, lambda: P.DeviceDelayTail(1, k), lambda ds: ds.read())
     reqs, delays = np.ascontiguousarray(c.reqs), np.ascontiguousarray(c.delays)
     host = reqs if fmt == A.PU_REQ_FMT_32 else U.pack_req16(reqs)
     assert_same((ent[0], cnt[0]), P.delay_tail(host, delays, k, fmt=fmt), f"{c.name}: device vs delay_tail")
@@ -445,14 +377,6 @@ def test_overflow_halt_golden_from_the_host_copy():
 
 
 # ---------------------------------------------------------------- the tool
-def _tool(*extra):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "ensemble_summary.py"), "--preset", "C1", "--kind", "1",
-                        "--replicas", "4", "--chunk", "2000", "--chunks", "2", *extra],
-                       capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return [x for x in r.stdout.splitlines() if x.startswith("{")]
-
-
 def test_ensemble_summary_tool_with_tail():
     """tools/ensemble_summary.py --tail 8 in a child process: its "slowest" lists and its last line equal
     delay_tail over a StreamSet -> run_device run of the same seeds; without --tail the output is that of
