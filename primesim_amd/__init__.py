@@ -1,8 +1,12 @@
 """primesim_amd — MI355X-native uncore timing engine for PriME's memory-system hot path.
 
 The product is the HIP engine in libprimeuncore.so (C ABI: include/primeuncore.h);
-this package is its Python host mirror (`uncore.UncoreManager`), the config_prime
-schema (`config`) and the ctypes ABI definitions (`_abi`).
+this package is its Python host mirror, the config_prime schema (`config`) and the
+ctypes ABI definitions (`_abi`: the record layouts and constants).  `_native` loads
+the library, holds the ctypes signature table and the one rule for turning an entry's
+return value into `UncoreError`; the mirror itself is by concern in `engine`
+(`UncoreManager`, the config loaders), `streams`, `traces`, `delays`, `results` and
+`msglog`, with `server` on top.  `uncore` re-exports all of it under one name.
 """
 from . import _abi, config  # noqa: F401
 from .uncore import (DeviceDelayHistogram, DeviceDelaySummary, DeviceDelayTail, DeviceRunResults, DeviceStreamSet, DeviceTraceSet, InsMem, StreamSet, StreamSpec, UncoreError, UncoreManager, config_from_dict,  # noqa: F401

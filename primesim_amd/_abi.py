@@ -1,6 +1,8 @@
 """ctypes mirror of include/primeuncore.h (structs, constants).
 
-Shared by the product binding (primesim_amd.uncore) and the test harness.
+Shared by the product binding (the signature table in primesim_amd._native and the
+modules that call it) and the test harness.  Each record layout is stated once, as a
+ctypes.Structure; the numpy dtype of a record is made from its Structure.
 """
 from __future__ import annotations
 
@@ -20,6 +22,7 @@ PU_STREAM_PRODUCER_CONSUMER = 5
 PU_STREAM_UNIFORM = 6
 
 PU_REQ_FMT_32, PU_REQ_FMT_16 = 0, 1      # device request records: pu_req, pu_req16
+PU_REPLAY_OPEN, PU_REPLAY_CLOSED = 0, 1  # pu_set_replay_mode
 
 PU_DSUM_BUCKETS = 32                     # delay summaries (pu_dsum_*)
 PU_DHIST_SUB_BITS, PU_DHIST_BUCKETS, PU_DHIST_MAX_Q = 5, 864, 8     # log-linear delay histograms (pu_dhist_*)
@@ -176,35 +179,14 @@ REQ_DTYPE = np.dtype([
     ("mem_type", "u1"), ("batch_start", "u1"), ("tag", "<u2"), ("_pad1", "<i4"),
 ])
 assert REQ_DTYPE.itemsize == 32
-# pu_dsum_class / pu_dsum_replica as numpy structured dtypes
-DSUM_CLASS_DTYPE = np.dtype([("count", "<u8"), ("sum", "<i8"), ("min", "<i4"), ("max", "<i4"),
-                             ("hist", "<u8", (PU_DSUM_BUCKETS,))])
-DSUM_DTYPE = np.dtype([("cls", DSUM_CLASS_DTYPE, (2,)), ("core_out_of_range", "<u8")])
-assert DSUM_DTYPE.itemsize == C.sizeof(DsumReplica) == 568
-# pu_dhist_quantile as a numpy structured dtype
-DHIST_Q_DTYPE = np.dtype([("count", "<u8"), ("bucket", "<i4", (PU_DHIST_MAX_Q,))])
-assert DHIST_Q_DTYPE.itemsize == C.sizeof(DhistQuantile) == 40
-# pu_dtail_entry as a numpy structured dtype
-DTAIL_DTYPE = np.dtype([("addr", "<u8"), ("timer", "<i8"), ("position", "<u8"), ("delay", "<i4"), ("core", "<i4")])
-assert DTAIL_DTYPE.itemsize == C.sizeof(DtailEntry) == 32
-# pu_level_stats / pu_stats / pu_dres_replica as numpy structured dtypes
-LEVEL_STATS_DTYPE = np.dtype([("ins", "<u8"), ("miss", "<u8"), ("evict", "<u8"), ("wb", "<u8")])
-STATS_DTYPE = np.dtype(
-    [(f, "<u8") for f in ("net_accesses", "net_distance", "net_total_delay", "net_router_delay", "net_link_delay",
-                          "net_inject_delay", "dram_accesses", "total_bus_contention")] +
-    [("total_num_broadcast", "<i8"), ("num_levels", "<i4"), ("_pad", "<i4"),
-     ("level", LEVEL_STATS_DTYPE, (PU_MAX_LEVELS,)), ("directory", LEVEL_STATS_DTYPE), ("tlb", LEVEL_STATS_DTYPE)] +
-    [(f, "<u8") for f in ("link_flits", "mg1_calls", "lockdown_calls", "bus_accesses", "requests", "error_flags",
-                          "dram_row_hits", "dram_row_empty", "dram_row_conflicts", "dram_bank_wait")])
-DRES_DTYPE = np.dtype([
-    ("stats", STATS_DTYPE), ("processed", "<u8"), ("halted", "<i4"), ("cores_done", "<i4"),
-    ("completion_max", "<i8"), ("completion_min", "<i8"), ("completion_sum", "<i8"),
-    ("link_visits", "<u8"), ("link_block_visits", "<u8"), ("link_max_visits", "<u8"),
-    ("link_max_id", "<i4"), ("links_used", "<i4"),
-    ("bus_visits", "<u8"), ("bus_max_visits", "<u8"), ("bus_max_id", "<i4"), ("buses_used", "<i4"),
-])
-assert STATS_DTYPE.itemsize == C.sizeof(Stats) == 352
-assert DRES_DTYPE.itemsize == C.sizeof(DresReplica) == 448
+# The records the readers return, as numpy structured dtypes: each is its Structure's layout
+DSUM_CLASS_DTYPE, DSUM_DTYPE = np.dtype(DsumClass), np.dtype(DsumReplica)
+DHIST_Q_DTYPE = np.dtype(DhistQuantile)
+DTAIL_DTYPE = np.dtype(DtailEntry)
+LEVEL_STATS_DTYPE, STATS_DTYPE, DRES_DTYPE = np.dtype(LevelStats), np.dtype(Stats), np.dtype(DresReplica)
+# the sizes pin the layouts to include/primeuncore.h
+assert C.sizeof(LevelStats) == 32 and C.sizeof(DtailEntry) == 32 and C.sizeof(DhistQuantile) == 40
+assert C.sizeof(Stats) == 352 and C.sizeof(DresReplica) == 448 and C.sizeof(DsumReplica) == 568
 PU_DRES_QUEUES = 1                       # pu_dres_open: keep the per-queue map
 PU_FORK_BY_COPIES = 1                    # pu_replica_fork: one device-to-device copy per destination
 assert C.sizeof(SimCfg) == 24 + C.sizeof(SysCfg)

@@ -22,9 +22,10 @@ from typing import Callable, Optional
 import numpy as np
 
 from . import _abi as A
-from .uncore import (MSG_MEM_REQUESTS, MSG_NEW_THREAD, MSG_PROCESS_FINISHING, MSG_PROCESS_STARTING,
-                     MSG_PROGRAM_EXITING, MSG_THREAD_FINISHING, MSGMEM_DTYPE, UncoreError, UncoreManager, last_error,
-                     lib)
+from ._native import call, counted, lib, opened
+from .engine import UncoreManager
+from .msglog import (MSG_MEM_REQUESTS, MSG_NEW_THREAD, MSG_PROCESS_FINISHING, MSG_PROCESS_STARTING,
+                     MSG_PROGRAM_EXITING, MSG_THREAD_FINISHING, MSGMEM_DTYPE)
 
 
 def _opts(socket_path: str, report_prefix: Optional[str], sessions: int, recv_threads: int, max_msg: int,
@@ -47,9 +48,7 @@ class PrimeServer:
         cfg = um.cfg
         self._o = _opts(socket_path, report_prefix, sessions, cfg.num_recv_threads, cfg.max_msg_size, verbose)
         self._keep = (um,)
-        self._h = lib().pu_server_create(um._handle(), C.byref(self._o))
-        if not self._h:
-            raise UncoreError(f"server: {last_error()}")
+        self._h = opened("pu_server_create", um._handle(), C.byref(self._o), context="server: ")
         self._thread: Optional[threading.Thread] = None
         self.rc: Optional[int] = None
 
@@ -77,18 +76,13 @@ class PrimeServer:
         self._cb = A.EXEC_FN(tramp)
         self._o = _opts(socket_path, None, sessions, recv_threads, max_msg, False)
         self._keep = ()
-        self._h = lib().pu_server_create_exec(self._cb, None, num_cores, C.byref(self._o))
-        if not self._h:
-            raise UncoreError(f"server: {last_error()}")
+        self._h = opened("pu_server_create_exec", self._cb, None, num_cores, C.byref(self._o), context="server: ")
         self._thread = None
         self.rc = None
         return self
 
     def round(self, timeout_ms: int = 0) -> int:
-        n = lib().pu_server_round(self._h, timeout_ms)
-        if n < 0:
-            raise UncoreError(f"server: {last_error()}")
-        return n
+        return counted("pu_server_round", self._h, timeout_ms, context="server: ")
 
     def run(self) -> int:
         return lib().pu_server_run(self._h)
@@ -129,19 +123,15 @@ class Client:
 
     def __init__(self, socket_path: str, session: int, rank: int):
         self.rank = rank
-        self._h = lib().pu_client_connect(socket_path.encode(), session, rank)
-        if not self._h:
-            raise UncoreError(f"client: {last_error()}")
+        self._h = opened("pu_client_connect", socket_path.encode(), session, rank, context="client: ")
 
     def send(self, records: np.ndarray, tag: int = 0) -> None:
         r = np.ascontiguousarray(records, dtype=MSGMEM_DTYPE)
-        if lib().pu_client_send(self._h, tag, r.ctypes.data, len(r)) != 0:
-            raise UncoreError(f"client: {last_error()}")
+        call("pu_client_send", self._h, tag, r.ctypes.data, len(r), context="client: ")
 
     def recv(self, tag: int) -> int:
         v = C.c_int32()
-        if lib().pu_client_recv(self._h, tag, C.byref(v)) != 0:
-            raise UncoreError(f"client: {last_error()}")
+        call("pu_client_recv", self._h, tag, C.byref(v), context="client: ")
         return v.value
 
     def control(self, message_type: int, mem_size: int = 0, tag: int = 0) -> None:
