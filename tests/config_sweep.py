@@ -1,6 +1,10 @@
-"""Small random configurations for tests/test_config_sweep_oracle.py: the draw
-(in the test's process) and one trial (a child process of its own, because the
-reference can crash where it is undefined):
+"""Small random configurations, drawn from one fixed seed: the one source of
+the draws for tests/test_config_sweep_oracle.py (the CPU restatement against
+the reference, on the CPU), tests/test_gpu_config_sweep.py (the engine kernels
+against the restatement, on the GPU) and the build-time warm-up
+(tools/jit_warm.py compiles `sweep_configs()`).  It holds the draw (in the
+test's process; no GPU) and, for the CPU sweep, one trial (a child process of
+its own, because the reference can crash where it is undefined):
 
     python tests/config_sweep.py <trial directory>
 
@@ -23,6 +27,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+SEED = 20260
+TRIALS = 64
 CORES = (1, 2, 3, 4, 8, 9, 12, 16, 27, 36, 64, 70)
 PU_ENOTSUP = -95   # include/primeuncore.h
 
@@ -92,6 +98,22 @@ def draw(rng: np.random.Generator) -> tuple:
             return sim, spec, replay, redraws
         assert rc == PU_ENOTSUP and "fill every parent" in text, f"the draw made a configuration refused for: {text}"
         redraws += 1
+
+
+def trials() -> list:
+    """The sweep's draws: what draw() gives for trial i's own generator, i in range(TRIALS)."""
+    return [draw(np.random.default_rng([SEED, i])) for i in range(TRIALS)]
+
+
+def sweep_configs() -> list:
+    """(name, SimCfg) of every trial, in the shape of extra_configs.extra_configs()."""
+    import primesim_amd as P
+    return [(f"sweep {i:02d}", P.config_from_dict(sim)) for i, (sim, _, _, _) in enumerate(trials())]
+
+
+def what(i: int, sim: dict, spec: dict, replay: str) -> str:
+    """How a failure names trial i."""
+    return f"trial {i} ({replay} replay, stream {spec}, configuration {json.dumps(sim['system'])})"
 
 
 def write_trial(path: str, sim: dict, spec: dict, replay: str) -> None:

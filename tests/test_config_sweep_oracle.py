@@ -11,7 +11,8 @@ child process of its own, at most 8 at a time, because the reference can crash
 where it is undefined.  A trial on which the restatement raises a
 reference-undefined flag counts as "undefined" and the reference is not run;
 on every other trial each delay, the return code and the completion cycles
-must be equal.
+must be equal.  The engine's six kernels run the same draws against the
+restatement on the GPU (tests/test_gpu_config_sweep.py).
 
 The share of undefined trials is bounded at 30 %: a 96-trial run of the same
 axes had 13 of the 83 trials the reference survived undefined (16 %), so a
@@ -23,14 +24,12 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-import numpy as np
 import pytest
 
 import oracle as O
 import config_sweep as CS
+from config_sweep import SEED, TRIALS
 
-SEED = 20260
-TRIALS = 64
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 pytestmark = pytest.mark.skipif(not O.ref_available(), reason="the reference's uncore is not compiled here")
@@ -44,8 +43,7 @@ def _child(path: str) -> tuple:
 
 def test_restatement_equals_reference_on_random_small_configurations(tmp_path):
     trials = []
-    for i in range(TRIALS):
-        sim, spec, replay, redraws = CS.draw(np.random.default_rng([SEED, i]))
+    for i, (sim, spec, replay, redraws) in enumerate(CS.trials()):
         path = str(tmp_path / f"trial{i:02d}")
         CS.write_trial(path, sim, spec, replay)
         trials.append((path, sim, spec, replay, redraws))
@@ -54,7 +52,7 @@ def test_restatement_equals_reference_on_random_small_configurations(tmp_path):
 
     signalled, differs, undefined, equal, requests = [], [], 0, 0, 0
     for i, ((path, sim, spec, replay, _), (rc, out, err)) in enumerate(zip(trials, results)):
-        what = f"trial {i} ({replay} replay, stream {spec}, configuration {json.dumps(sim['system'])})"
+        what = CS.what(i, sim, spec, replay)
         if rc < 0:
             signalled.append(f"{what}: the child died of signal {-rc}")
             continue

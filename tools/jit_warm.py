@@ -1,6 +1,7 @@
 """Warm the compile-time-configuration cache (primesim_amd/jit_cache/) for every
 configuration the GPU tests, smoke() and bench.py use: the golden XMLs, the
-C1-C5 presets, the DRAM-bank test geometries, tests/extra_configs.py and tests/pair_window_cases.py.  Runs on the CPU (hipcc, in a
+C1-C5 presets, the DRAM-bank test geometries, tests/extra_configs.py, tests/pair_window_cases.py and the
+seeded sweep's 64 draws (tests/config_sweep.py).  Runs on the CPU (hipcc, in a
 child process of each worker; no GPU), several compiles at once; a configuration already cached is skipped.
 A same-box A/B of compile options (tools/gpu_session.sh V@FLAGS) compiles its variant with hipRTC on the
 GPU box unless the variant is warmed here first with the same environment:
@@ -50,6 +51,11 @@ def configs():
     try:
         from pair_window_cases import pair_window_configs
         out.extend(pair_window_configs())
+    except ImportError:
+        pass
+    try:
+        from config_sweep import sweep_configs
+        out.extend(sweep_configs())
     except ImportError:
         pass
     return [(n, c, "") for n, c in out] + extra_option_configs()
