@@ -1093,6 +1093,12 @@ int pu_unit_queue_run(uint64_t min_proc, const uint64_t* t, const uint64_t* p, s
  * wait_out[i] = the queue delay.  The arithmetic fuzz of the M/G/1 branch. */
 int pu_unit_mg1_run(const uint64_t* num_arrivals, const double* sum, const double* sum_sq,
                     const uint64_t* newest, size_t n, uint64_t* wait_out, int device);
+/* The same, and which way the arithmetic went: path_out[i] = 1 when the
+ * one-division closed form was proven to give the reference's wait (its guard
+ * held), 0 when the reference's own five-division chain ran. */
+int pu_unit_mg1_path_run(const uint64_t* num_arrivals, const double* sum, const double* sum_sq,
+                         const uint64_t* newest, size_t n, uint64_t* wait_out, uint8_t* path_out,
+                         int device);
 /* Network::transmit sequence on a fresh mesh (network.cpp:97-160); st gets
  * the network counters. */
 int pu_unit_network_run(int num_nodes, int net_type, int data_width, int header_flits,

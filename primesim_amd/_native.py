@@ -176,6 +176,8 @@ SIGNATURES = {
     "pu_client_close": (None, [C.c_void_p]),
     "pu_unit_mg1_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                   C.c_int]),
+    "pu_unit_mg1_path_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_void_p, C.c_int]),
     "pu_unit_queue_run": (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                     P(C.c_uint64), C.c_int]),
     "pu_unit_network_run": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
@@ -183,8 +185,8 @@ SIGNATURES = {
                                       P(A.Stats), C.c_int]),
 }
 del P
-# diagnostics only: libraries of older commits (same-box A/B variants) lack it
-OPTIONAL = ("pu_jit_prof_read",)
+# diagnostics and test hooks only: libraries of older commits (same-box A/B variants) lack them
+OPTIONAL = ("pu_jit_prof_read", "pu_unit_mg1_path_run")
 
 
 class UncoreError(RuntimeError):

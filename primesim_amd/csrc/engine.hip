@@ -404,7 +404,9 @@ enum ProfId {
     PF_LOOP, PF_REQ, PF_NET, PF_NSETUP, PF_NHOPS, PF_NTREE, PF_NWAIT, PF_NWB, PF_SETL0, PF_SETLN, PF_HOME_LD,
     PF_HOME, PF_DOWN, PF_WINDOWS, PF_TREEHOPS, PF_DEMAND, PF_T_LDS, PF_T_SEARCH, PF_T_DECIDE, PF_T_EDIT,
     PF_T_STORE, PF_T_REFILL, PF_NPRE, PF_NPOST, PF_MG1RUN, PF_MG1LANES, PF_MG1HITS, PF_MAINTAIL,
-    PF_MG1PRESENT, PF_MG1STORED, PF_MG1BATCH, PF_T_UPD, PF_COUNT
+    PF_MG1PRESENT, PF_MG1STORED, PF_MG1BATCH, PF_T_UPD,
+    PF_MG1CALLS, PF_MG1CHAIN,   // mg1_wait calls, and those in which a lane's guard failed (the chain ran)
+    PF_COUNT
 };
 #ifdef PU_PROF
 static __shared__ unsigned long long lds_prof[PF_COUNT];
@@ -509,8 +511,9 @@ __device__ __forceinline__ double div_nr(double a, double b, double y) {
     return __builtin_fma(__builtin_fma(-b, q, a), y, q);
 }
 
-// M/G/1 (queue_model_m_g_1.cpp:16-42), reference operation order.
-__device__ __forceinline__ uint64_t mg1_wait(const QState& s) {
+// M/G/1 (queue_model_m_g_1.cpp:16-42), reference operation order: the five
+// divisions of the reference, each correctly rounded.  mg1_wait's fallback.
+__device__ __forceinline__ uint64_t mg1_wait_exact(const QState& s) {
     if (s.n == 0.0) return 0;
     const double nd = s.n;
     const double rn = rcp_nr(nd);
@@ -528,6 +531,64 @@ __device__ __forceinline__ uint64_t mg1_wait(const QState& s) {
     const double den = mu - lambda;
     double w = div_nr(num, den, rcp_nr(den));
     return (uint64_t)ceil(w);
+}
+
+// The guard of mg1_wait ("Floating point").  The chain above is
+// Pollaczek-Khinchine: in exact arithmetic its w is sum_sq / (2 (newest - sum)),
+// or 499.5 sum_sq / sum under the 0.999 clamp (sum >= newest), and n cancels.
+// The chain's own w lies within PU_MG1_GUARD_C * 2^-53 / (1 - rho) of that
+// (rho = sum / newest; * 1000 when clamped), the one-division w here included,
+// so when no integer lies that close to it, its ceil is the chain's.
+#define PU_MG1_GUARD_C 64.0
+// |newest - sum| up to 2^-48 newest + 2: the chain compares two rounded
+// quotients, and the clamp can fall either way
+#define PU_MG1_DOUBT_REL 0x1p-48
+#define PU_MG1_DOUBT_ABS 2.0
+
+// The wait of the closed form and whether it is certainly the chain's.  The
+// bound needs the moments to be what a queue accumulates: integer sums of
+// packet lengths >= 1 and of their squares, below 2^53 (so exact, and
+// sum^2 <= n sum_sq holds).  The engine's headers hold nothing else below
+// 2^53; CHECK tests all of it, for states given from outside (the unit hook).
+template <bool CHECK>
+__device__ __forceinline__ bool mg1_wait_fast(const QState& s, uint64_t& wait) {
+    const double nw = (double)s.newest;      // off by 2^-53 newest at most, and only above 2^53 > sum
+    const bool clamp = s.sum >= nw;
+    const double gap = nw - s.sum;
+    const double den = clamp ? s.sum : gap;
+    const double num = (clamp ? 499.5 : 0.5) * s.sum_sq;
+    // one Newton step and the residual correction: within 2^-52 of num / den
+    // wherever v_rcp_f64 is within 2^-14 of 1 / den
+    double y = __builtin_amdgcn_rcp(den);
+    y = __builtin_fma(y, __builtin_fma(-den, y, 1.0), y);
+    const double w = div_nr(num, den, y);
+    const double c = ceil(w);
+    // nw * y = 1 / (1 - rho) when not clamped
+    const double g = clamp ? PU_MG1_GUARD_C * 0x1p-53 * 1000.0 : (PU_MG1_GUARD_C * 0x1p-53) * (nw * y);
+    bool ok = __builtin_fma(w, g, w) <= c && __builtin_fma(-w, g, w) > c - 1.0;   // fails by itself from w = 2^52 on
+    ok = ok && __builtin_fabs(gap) > __builtin_fma(nw, PU_MG1_DOUBT_REL, PU_MG1_DOUBT_ABS);
+    ok = ok && s.sum_sq < 0x1p53 && s.sum < 0x1p53 && s.sum >= 1.0;   // (0-flit packets alone: the chain's NaN)
+    if constexpr (CHECK)
+        ok = ok && __builtin_trunc(s.sum) == s.sum && __builtin_trunc(s.sum_sq) == s.sum_sq &&
+             s.sum * s.sum <= (s.n * s.sum_sq) * (1.0 + 0x1p-50);
+    wait = (uint64_t)c;   // meaningful only when ok (c is then an integer in [1, 2^52)); not read otherwise
+    return ok;
+}
+
+// M/G/1 (queue_model_m_g_1.cpp:16-42): one guarded division, and the
+// reference's own chain for the lanes whose guard does not hold (a wave where
+// every lane's does skips it).  Bit-identical to the chain either way.
+template <bool CHECK = false>
+__device__ __forceinline__ uint64_t mg1_wait(const QState& s, bool* accepted = nullptr) {
+    if (accepted) *accepted = false;
+    if (s.n == 0.0) return 0;
+    uint64_t w;
+    const bool chain = !mg1_wait_fast<CHECK>(s, w);
+    PROF_CNT(PF_MG1CALLS, 1);
+    PROF_CNT(PF_MG1CHAIN, ballot(chain) != 0);
+    if (chain) return mg1_wait_exact(s);
+    if (accepted) *accepted = true;
+    return w;
 }
 
 // Whole-wave rotates (DPP): lane i receives lane (i+1)&63 / (i-1)&63.
@@ -3463,21 +3524,39 @@ __global__ __launch_bounds__(64) void unit_network_kernel(const Geo* __restrict_
 // once, one state per lane: the arithmetic fuzz of tests/test_gpu_mg1.py.  n is
 // the reference's UInt64 _num_arrivals, held by the engine as an exact double
 // (n < 2^53, checked by the caller).
+__device__ __forceinline__ QState unit_mg1_state(uint64_t n, double sum, double sum_sq, uint64_t newest) {
+    QState s;
+    s.head = 0;
+    s.count = 0;
+    s.n = (double)n;
+    s.sum = sum;
+    s.sum_sq = sum_sq;
+    s.newest = newest;
+    s.f0 = 0;
+    s.sum1 = 0.0;
+    return s;
+}
 __global__ __launch_bounds__(256) void unit_mg1_kernel(const uint64_t* __restrict__ n, const double* __restrict__ sum,
                                                        const double* __restrict__ sum_sq,
                                                        const uint64_t* __restrict__ newest, uint64_t cnt,
                                                        uint64_t* __restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cnt) return;
-    QState s;
-    s.head = 0;
-    s.count = 0;
-    s.n = (double)n[i];
-    s.sum = sum[i];
-    s.sum_sq = sum_sq[i];
-    s.newest = newest[i];
-    s.f0 = 0;
-    out[i] = mg1_wait(s);
+    out[i] = mg1_wait<true>(unit_mg1_state(n[i], sum[i], sum_sq[i], newest[i]));
+}
+
+// The same, and which way each state went: path[i] = 1 when mg1_wait's guard
+// held (the one-division wait), 0 when the reference's chain ran.
+__global__ __launch_bounds__(256) void unit_mg1_path_kernel(const uint64_t* __restrict__ n,
+                                                            const double* __restrict__ sum,
+                                                            const double* __restrict__ sum_sq,
+                                                            const uint64_t* __restrict__ newest, uint64_t cnt,
+                                                            uint64_t* __restrict__ out, uint8_t* __restrict__ path) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    bool fast;
+    out[i] = mg1_wait<true>(unit_mg1_state(n[i], sum[i], sum_sq[i], newest[i]), &fast);
+    path[i] = fast ? 1 : 0;
 }
 
 // Sharer-bitmap pool: free stack [0, P) and RunState.pool_top = P per replica.
@@ -3512,11 +3591,15 @@ extern "C" int pu_engine_unit_queue(const Geo* d_geo, char* base, uint64_t minp,
     return hipGetLastError() == hipSuccess ? 0 : PU_EIO;
 }
 
+// path: null, or one byte per state (unit_mg1_path_kernel)
 extern "C" int pu_engine_unit_mg1(const uint64_t* n, const double* sum, const double* sum_sq, const uint64_t* newest,
-                                  uint64_t cnt, uint64_t* out, hipStream_t s) {
+                                  uint64_t cnt, uint64_t* out, uint8_t* path, hipStream_t s) {
     if (cnt == 0) return 0;
-    hipLaunchKernelGGL(unit_mg1_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, n, sum, sum_sq, newest,
-                       cnt, out);
+    const dim3 grid((unsigned)((cnt + 255) / 256));
+    if (path)
+        hipLaunchKernelGGL(unit_mg1_path_kernel, grid, dim3(256), 0, s, n, sum, sum_sq, newest, cnt, out, path);
+    else
+        hipLaunchKernelGGL(unit_mg1_kernel, grid, dim3(256), 0, s, n, sum, sum_sq, newest, cnt, out);
     return hipGetLastError() == hipSuccess ? 0 : PU_EIO;
 }
 

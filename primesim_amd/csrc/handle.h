@@ -29,7 +29,7 @@ extern "C" int pu_engine_init_pool(char* arena, uint64_t replica_bytes, uint64_t
 extern "C" int pu_engine_unit_queue(const Geo* d_geo, char* base, uint64_t minp, const uint64_t* t,
                                     const uint64_t* p, uint64_t n, uint64_t* out, uint64_t* mg1, hipStream_t s);
 extern "C" int pu_engine_unit_mg1(const uint64_t* n, const double* sum, const double* sum_sq, const uint64_t* newest,
-                                  uint64_t cnt, uint64_t* out, hipStream_t s);
+                                  uint64_t cnt, uint64_t* out, uint8_t* path, hipStream_t s);
 extern "C" int pu_engine_unit_network(const Geo* d_geo, char* base, const int32_t* src, const int32_t* dst,
                                       const int32_t* len, const uint64_t* timer, uint64_t n, uint64_t* out,
                                       hipStream_t s);

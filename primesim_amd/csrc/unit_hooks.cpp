@@ -80,6 +80,11 @@ int pu_unit_queue_run(uint64_t min_proc, const uint64_t* t, const uint64_t* p, s
 
 int pu_unit_mg1_run(const uint64_t* num_arrivals, const double* sum, const double* sum_sq, const uint64_t* newest,
                     size_t n, uint64_t* wait_out, int device) {
+    return pu_unit_mg1_path_run(num_arrivals, sum, sum_sq, newest, n, wait_out, nullptr, device);
+}
+
+int pu_unit_mg1_path_run(const uint64_t* num_arrivals, const double* sum, const double* sum_sq,
+                         const uint64_t* newest, size_t n, uint64_t* wait_out, uint8_t* path_out, int device) {
     if ((!num_arrivals || !sum || !sum_sq || !newest || !wait_out) && n) return pu::set_error(PU_EINVAL, "bad arguments");
     for (size_t i = 0; i < n; i++)
         if (num_arrivals[i] >= (1ull << 53))   // the engine holds the count as an exact double
@@ -92,11 +97,13 @@ int pu_unit_mg1_run(const uint64_t* num_arrivals, const double* sum, const doubl
     double* dq = b.up(sum_sq, n);
     uint64_t* dw = b.up(newest, n);
     uint64_t* dout = b.up<uint64_t>(nullptr, n);
-    if (n && (!dn || !ds || !dq || !dw || !dout)) return pu::set_error(PU_ENOMEM, "unit buffers");
-    rc = pu_engine_unit_mg1(dn, ds, dq, dw, n, dout, nullptr);
+    uint8_t* dpath = path_out ? b.up<uint8_t>(nullptr, n) : nullptr;
+    if (n && (!dn || !ds || !dq || !dw || !dout || (path_out && !dpath))) return pu::set_error(PU_ENOMEM, "unit buffers");
+    rc = pu_engine_unit_mg1(dn, ds, dq, dw, n, dout, dpath, nullptr);
     if (rc) return pu::set_error(rc, "unit M/G/1 launch failed");
     HIP_TRY(hipDeviceSynchronize(), PU_EIO);
     if (n) HIP_TRY(hipMemcpy(wait_out, dout, n * 8, hipMemcpyDeviceToHost), PU_EIO);
+    if (n && path_out) HIP_TRY(hipMemcpy(path_out, dpath, n, hipMemcpyDeviceToHost), PU_EIO);
     return 0;
 }
 
