@@ -957,6 +957,78 @@ int       pu_dtail_k(const pu_dtail* s);
 int       pu_dtail_host_add(pu_dtail_entry* entries /*[2][k]*/, uint32_t* counts /*[2]*/, uint64_t* seen,
                             int k, const void* reqs, int fmt, const int32_t* delays, size_t n);
 
+/* Every replica's delays over simulated time kept on the device (no reference counterpart;
+ * one more stage on the same stream: ... -> pu_dsum_add -> pu_dhist_add -> pu_dtail_add ->
+ * pu_dseries_add).  The summaries, histograms and lists fold a replica's whole measured
+ * range into one figure; these series say when: per replica, class and epoch of the records'
+ * own timers the count, the exact sum, the largest delay and the number of non-positive
+ * delays, still without a request or a delay on the host.  At which cycle an open-loop
+ * replica's delays start to climb, where it halted, how long a warm-up lasts: a user divides
+ * sum by count per epoch.  Every figure is an exact integer and independent of the order of
+ * the records, so the device result equals the host fold (pu_dseries_host_add) bit for bit,
+ * and cells merge fieldwise: chunks, replicas and ranks add what they read (max: the larger).
+ *
+ * The rule (primesim_amd/csrc/delay_series_step.h):
+ *   set       `count` replicas, E epochs (1 <= E <= PU_DSERIES_MAX_EPOCHS), a first cycle t0
+ *             (any int64) and a shift (0 .. 62), fixed at open.  An epoch is 2^shift cycles.
+ *   class     as for pu_dsum_*: 0 = read, 1 = write (pu_req: mem_type == PU_WR).
+ *   timer     the record's own: pu_req.timer, or PU_REQ16_TIMER(b) of a pu_req16.
+ *   epoch     0 for timer < t0; otherwise min(((uint64_t)timer - (uint64_t)t0) >> shift, E - 1).
+ *             The distance is taken unsigned, so INT64_MAX against t0 = INT64_MIN is defined.
+ *             The first and the last epoch are catch-alls: no record is dropped, and a
+ *             replica's cells add up to what pu_dsum_* reports for the same records.
+ *   cell      count: the records; sum: of every delay, non-positive ones included; nonpos: the
+ *             delays <= 0 (the zeros a halted replica's remaining range reads, the -1 of a core
+ *             id out of range, wrapped delays: what pu_dsum's bucket 0 counts); max: the
+ *             largest of max(delay, 0).  An empty cell is all-zero bytes.
+ *   layout    pu_dseries_cell cells[2][E] per replica (64 E bytes).
+ *   total     the cells of replicas [first, first + n) merged: count, sum and nonpos added,
+ *             max the largest.
+ *
+ * pu_dseries_open: `count` replicas with E epochs on `device`; 64 E bytes of device memory per
+ * replica plus the slabs of the ensemble total.  NULL + pu_last_error() on failure (count < 1,
+ * epochs outside 1 .. PU_DSERIES_MAX_EPOCHS or shift outside 0 .. 62: before a device is
+ * touched; "no HIP device" where there is none: the set has no CPU fallback).
+ *
+ * pu_dseries_add: replica r folds records [d_begin[r], d_end[r]) into its cells; the
+ * arguments, their checks (d_reqs 16-byte aligned) and the ordering are pu_dsum_add's, so one
+ * pair of index arrays serves all four calls.
+ *
+ * pu_dseries_read: the cells of replicas [first, first + n): out holds n * 2 * E cells,
+ * [replica][class][epoch].  pu_dseries_read_total: the ensemble total of replicas
+ * [first, first + n) (2 * E cells; all zero for n = 0), formed when read by two launches
+ * without atomics on the set's own stream.  pu_dseries_reset: every cell back to zero.
+ * pu_dseries_state_bytes: device memory the set holds.  pu_dseries_epochs: E (0 for NULL).
+ * Reading, resetting and closing wait only for the work of this set.  A NULL set: PU_EINVAL,
+ * 0, no-op; first < 0, n < 0 or a NULL output with n > 0: PU_EINVAL; first + n > count:
+ * PU_ERANGE.
+ *
+ * Host twins, no device needed.  pu_dseries_host_add: n records folded into one replica's
+ * cells ([2][epochs], zeroed by the caller before the first call).  pu_dseries_epoch_of: the
+ * epoch of a timer; PU_EINVAL for epochs or shift out of range. */
+#define PU_DSERIES_MAX_EPOCHS 512
+typedef struct pu_dseries_cell {
+    uint64_t count;     /* records of the class in the epoch */
+    int64_t  sum;       /* of every delay */
+    uint64_t nonpos;    /* delays <= 0 */
+    int32_t  max;       /* the largest of max(delay, 0) */
+    int32_t  _pad;
+} pu_dseries_cell;      /* 32 bytes */
+
+typedef struct pu_dseries pu_dseries;
+pu_dseries* pu_dseries_open(int count, int epochs, int64_t t0, int shift, int device);
+void        pu_dseries_close(pu_dseries* s);
+int         pu_dseries_add(pu_dseries* s, const void* d_reqs, int fmt, const int32_t* d_delay,
+                           const uint64_t* d_begin, const uint64_t* d_end, void* hip_stream);
+int         pu_dseries_read(pu_dseries* s, int first, int n, pu_dseries_cell* out /*[n][2][E]*/);
+int         pu_dseries_read_total(pu_dseries* s, int first, int n, pu_dseries_cell* out /*[2][E]*/);
+int         pu_dseries_reset(pu_dseries* s);
+uint64_t    pu_dseries_state_bytes(const pu_dseries* s);
+int         pu_dseries_epochs(const pu_dseries* s);
+int         pu_dseries_host_add(pu_dseries_cell* cells /*[2][epochs]*/, int epochs, int64_t t0, int shift,
+                                const void* reqs, int fmt, const int32_t* delays, size_t n);
+int         pu_dseries_epoch_of(int64_t timer, int epochs, int64_t t0, int shift);
+
 /* Trace files ("PUTRACE1": header, thread table, pu_req records). */
 int pu_trace_write(const char* path, const pu_req* reqs, size_t n,
                    const int32_t* thread_prog, const int32_t* thread_id, int num_threads);

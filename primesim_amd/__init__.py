@@ -14,6 +14,8 @@ from .uncore import (DeviceDelayHistogram, DeviceDelaySummary, DeviceDelayTail, 
                      pack_req16, stream_fits_req16, stream_threads, summarize_delays, MsgLogWriter,
                      host_run_results, queue_ends, delay_histogram, histogram_quantiles, dhist_bucket_of,
                      dhist_bucket_bounds, delay_tail, place_trace, placement_seed, random_placements)
+# bound as attributes, not listed: __all__ is pinned by tests/test_python_mirror.py
+from .uncore import DeviceDelaySeries, delay_series, dseries_epoch_of  # noqa: F401
 
 __all__ = ["DeviceDelayHistogram", "DeviceDelaySummary", "DeviceDelayTail", "DeviceRunResults", "DeviceStreamSet", "DeviceTraceSet", "InsMem", "StreamSet", "StreamSpec", "UncoreError", "UncoreManager", "config_from_dict", "generate_stream",
            "load_config", "msglog_from_stream", "msglog_read", "MsgLogWriter", "pack_req16", "parse_config",

@@ -27,6 +27,7 @@ PU_REPLAY_OPEN, PU_REPLAY_CLOSED = 0, 1  # pu_set_replay_mode
 PU_DSUM_BUCKETS = 32                     # delay summaries (pu_dsum_*)
 PU_DHIST_SUB_BITS, PU_DHIST_BUCKETS, PU_DHIST_MAX_Q = 5, 864, 8     # log-linear delay histograms (pu_dhist_*)
 PU_DTAIL_MAX_K = 64                      # the longest list of slowest requests (pu_dtail_*)
+PU_DSERIES_MAX_EPOCHS = 512              # the most epochs of an epoch series (pu_dseries_*)
 
 PU_ERRF_CORE_RANGE = 1 << 0
 PU_ERRF_WB_MISS = 1 << 1
@@ -143,6 +144,11 @@ class DtailEntry(C.Structure):          # pu_dtail_entry
                 ("core", C.c_int32)]
 
 
+class DseriesCell(C.Structure):         # pu_dseries_cell
+    _fields_ = [("count", C.c_uint64), ("sum", C.c_int64), ("nonpos", C.c_uint64), ("max", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
 class DresReplica(C.Structure):         # pu_dres_replica
     _fields_ = [
         ("stats", Stats), ("processed", C.c_uint64), ("halted", C.c_int32), ("cores_done", C.c_int32),
@@ -183,9 +189,11 @@ assert REQ_DTYPE.itemsize == 32
 DSUM_CLASS_DTYPE, DSUM_DTYPE = np.dtype(DsumClass), np.dtype(DsumReplica)
 DHIST_Q_DTYPE = np.dtype(DhistQuantile)
 DTAIL_DTYPE = np.dtype(DtailEntry)
+DSERIES_DTYPE = np.dtype(DseriesCell)
 LEVEL_STATS_DTYPE, STATS_DTYPE, DRES_DTYPE = np.dtype(LevelStats), np.dtype(Stats), np.dtype(DresReplica)
 # the sizes pin the layouts to include/primeuncore.h
 assert C.sizeof(LevelStats) == 32 and C.sizeof(DtailEntry) == 32 and C.sizeof(DhistQuantile) == 40
+assert C.sizeof(DseriesCell) == 32
 assert C.sizeof(Stats) == 352 and C.sizeof(DresReplica) == 448 and C.sizeof(DsumReplica) == 568
 PU_DRES_QUEUES = 1                       # pu_dres_open: keep the per-queue map
 PU_FORK_BY_COPIES = 1                    # pu_replica_fork: one device-to-device copy per destination

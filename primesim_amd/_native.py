@@ -146,6 +146,17 @@ SIGNATURES = {
     "pu_dtail_k": (C.c_int, [C.c_void_p]),
     "pu_dtail_host_add": (C.c_int, [P(A.DtailEntry), P(C.c_uint32), P(C.c_uint64), C.c_int, C.c_void_p, C.c_int,
                                     P(C.c_int32), C.c_size_t]),
+    "pu_dseries_open": (C.c_void_p, [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int]),
+    "pu_dseries_close": (None, [C.c_void_p]),
+    "pu_dseries_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pu_dseries_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(A.DseriesCell)]),
+    "pu_dseries_read_total": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(A.DseriesCell)]),
+    "pu_dseries_reset": (C.c_int, [C.c_void_p]),
+    "pu_dseries_state_bytes": (C.c_uint64, [C.c_void_p]),
+    "pu_dseries_epochs": (C.c_int, [C.c_void_p]),
+    "pu_dseries_host_add": (C.c_int, [P(A.DseriesCell), C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, P(C.c_int32),
+                                      C.c_size_t]),
+    "pu_dseries_epoch_of": (C.c_int, [C.c_int64, C.c_int, C.c_int64, C.c_int]),
     "pu_dres_open": (C.c_void_p, [C.c_void_p, C.c_int]),
     "pu_dres_close": (None, [C.c_void_p]),
     "pu_dres_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -1,8 +1,8 @@
-// delay_stage.h — what the three delay stages (delay_sum.hip, delay_hist.hip,
-// delay_tail.hip) share below device_set.h: every one folds each replica's records
-// [d_begin[r], d_end[r]) of one request array and one delay array, by one launch
-// per call with one workgroup of kThreads per replica.  Included by those three
-// files only; everything is local to the file that includes it.
+// delay_stage.h — what the four delay stages (delay_sum.hip, delay_hist.hip,
+// delay_tail.hip, delay_series.hip) share below device_set.h: every one folds each
+// replica's records [d_begin[r], d_end[r]) of one request array and one delay array,
+// by one launch per call with one workgroup of kThreads per replica.  Included by
+// those four files only; everything is local to the file that includes it.
 //
 // Device side.  RecordRange is the workgroup's range and RecordSource loads its
 // records: lanes take consecutive records, kUnroll per lane and trip.  Of the
@@ -11,7 +11,9 @@
 //   the class alone       8 B: pu_req16.b, or the last word of a pu_req (mem_type | ...)
 //   the core id as well   pu_req16.b again (8 B), or the second half of a pu_req
 //                         (16 B: core | prog_id, mem_type | ...)
-// In every case that is the record's last word of its size, so one stride
+//   the timer as well     pu_req16.b again (8 B), or two 8-B words of a pu_req (timer,
+//                         mem_type | ...): TimedRecordSource, the epoch series' own
+// In the first two cases that is the record's last word of its size, so one stride
 // arithmetic serves.  The trip loop and the accumulation are the stage's: the
 // helpers here are straight-line on purpose.  They are inlined after they have been
 // optimised on their own, and a loop or a decode of two fields moved in here
@@ -102,6 +104,44 @@ struct RecordSource {
         static_assert(!CORE, "a word with the core id is taken apart by its stage");
         return FMT == PU_REQ_FMT_16 ? pu_delay_record::class_of_req16_b(w)
                                     : pu_delay_record::class_of_mem_type((uint32_t)(w & 0xFFu));
+    }
+};
+
+// The same range for a stage that asks for a record's timer beside its class (the epoch
+// series, delay_series.hip): of a pu_req16 the word b alone, as above (8 B: the timer is in
+// its low bits); of a pu_req the timer (offset 8) and the last word (offset 24), two 8-B
+// loads in the one 32-B record, so the lines touched are those of RecordSource.  A source of
+// its own, so that RecordSource instantiates for the other three stages what it always did.
+template <int FMT>
+struct TimedRecordSource {
+    static constexpr int kStride = (int)((FMT == PU_REQ_FMT_16 ? sizeof(pu_req16) : sizeof(pu_req)) / sizeof(u64));
+    static constexpr int kTimerWord = 1;   // pu_req.timer
+
+    const int32_t* dl;
+    const u64* wd;   // the range's first record
+    uint64_t len;
+
+    __device__ TimedRecordSource(const void* reqs, const int32_t* delay, uint64_t b, uint64_t len_)
+        : dl(delay + b), wd((const u64*)reqs + (uint64_t)kStride * b), len(len_) {}
+
+    // Record i of the range into (d, t, w): w the record's last word, t the timer word of a
+    // pu_req (0 for a pu_req16, whose timer is in w); false, and zeros, at and past the range's end.
+    __device__ bool load(uint64_t i, int32_t& d, u64& t, u64& w) const {
+        const bool valid = i < len;
+        d = 0;
+        t = 0;
+        w = 0;
+        if (valid) {
+            d = dl[i];
+            w = wd[(uint64_t)kStride * i + (kStride - 1)];
+            if constexpr (FMT == PU_REQ_FMT_32) t = wd[(uint64_t)kStride * i + kTimerWord];
+        }
+        return valid;
+    }
+
+    __device__ static int cls(u64 w) { return RecordSource<FMT, false>::cls(w); }
+    __device__ static int64_t timer(u64 t, u64 w) {
+        return FMT == PU_REQ_FMT_16 ? pu_delay_record::timer_of_req16_b(w) : (int64_t)t;
     }
 };
 

@@ -1,5 +1,5 @@
 // device_set.h — what the device-side ensemble stages (stream_gen.hip, trace_place.hip,
-// delay_sum.hip, delay_hist.hip, delay_tail.hip, run_results.hip) share on the host: one allocation of device state per set, the
+// delay_sum.hip, delay_hist.hip, delay_tail.hip, delay_series.hip, run_results.hip) share on the host: one allocation of device state per set, the
 // set's own stream, and the rule that orders the set's calls whatever stream
 // each is given.  A stage's handle derives from DeviceSet and adds what is its
 // own.  Host code only: the stage files include it, engine.hip does not.
@@ -11,7 +11,7 @@
 // nothing.  Reading back and closing wait for `ev` on the host, so only for the
 // set's own work.
 //
-// replica_range is the readers' check of first and n against the set.  What the three
+// replica_range is the readers' check of first and n against the set.  What the four
 // delay stages share beyond that, the record reader of their kernels and delay_add
 // around their launches, is in delay_stage.h.
 #pragma once

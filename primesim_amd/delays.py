@@ -1,6 +1,6 @@
 """What an ensemble's (request, delay) pairs fold into: summaries (pu_dsum_*), log-linear
-histograms (pu_dhist_*) and the slowest requests (pu_dtail_*), each as a host fold and as a
-set kept on the device."""
+histograms (pu_dhist_*), the slowest requests (pu_dtail_*) and series over simulated time
+(pu_dseries_*), each as a host fold and as a set kept on the device."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,7 +9,7 @@ from typing import Optional
 import numpy as np
 
 from . import _abi as A
-from ._native import UncoreError, _as, _DeviceSet, call, lib
+from ._native import UncoreError, _as, _DeviceSet, call, counted, lib
 
 
 def _records(reqs: np.ndarray, delays: np.ndarray, fmt: int) -> tuple[np.ndarray, np.ndarray]:
@@ -24,7 +24,7 @@ def _records(reqs: np.ndarray, delays: np.ndarray, fmt: int) -> tuple[np.ndarray
 
 
 class _DelayStage(_DeviceSet):
-    """What the three delay stages share: the entries `<_prefix>_add` and `<_prefix>_reset`."""
+    """What the four delay stages share: the entries `<_prefix>_add` and `<_prefix>_reset`."""
 
     def add(self, d_reqs_ptr: int, d_delay_ptr: int, d_begin_ptr: int, d_end_ptr: int, fmt: int = A.PU_REQ_FMT_32,
             stream_ptr: int = 0) -> None:
@@ -234,3 +234,64 @@ class DeviceDelayTail(_DelayStage):
         self._call("read_total", first, self._count(first, n), _as(entries, A.DtailEntry), _as(replicas, C.c_int32),
                    _as(counts, C.c_uint32))
         return entries, replicas, counts
+
+
+# ---------------------------------------------------------------- epoch series
+def dseries_epoch_of(timer: int, epochs: int, t0: int = 0, shift: int = 0) -> int:
+    """The epoch of a record's timer in a series of `epochs` epochs of 2^shift cycles from t0
+    (pu_dseries_epoch_of; the rule is in include/primeuncore.h)."""
+    return counted("pu_dseries_epoch_of", int(timer), int(epochs), int(t0), int(shift))
+
+
+def delay_series(reqs: np.ndarray, delays: np.ndarray, epochs: int, t0: int = 0, shift: int = 0,
+                 fmt: int = A.PU_REQ_FMT_32, acc=None) -> np.ndarray:
+    """The host fold of (request, delay) pairs into one replica's epoch series
+    (pu_dseries_host_add; the rule is in include/primeuncore.h): A.DSERIES_DTYPE [2, epochs],
+    reads and writes apart, per epoch of the records' own timers count, sum, nonpos (delays
+    <= 0) and max (the largest of max(delay, 0)).  acc, an array an earlier call returned for
+    the same epochs, is continued (and left unchanged).  reqs as for summarize_delays.
+    Needs no device."""
+    reqs, delays = _records(reqs, delays, fmt)
+    epochs = int(epochs)
+    if acc is None:
+        cells = np.zeros((2, max(epochs, 1)), dtype=A.DSERIES_DTYPE)
+    else:
+        cells = acc.copy()
+        if cells.shape != (2, epochs) or cells.dtype != A.DSERIES_DTYPE:
+            raise UncoreError(f"delay_series: acc is not the result of a call with epochs = {epochs}")
+    call("pu_dseries_host_add", _as(cells, A.DseriesCell), epochs, int(t0), int(shift), reqs.ctypes.data, fmt,
+         _as(delays, C.c_int32), len(delays))
+    return cells
+
+
+class DeviceDelaySeries(_DelayStage):
+    """Per-replica delays over simulated time kept on the device (pu_dseries_*): `add` folds
+    every replica's records [begin[r], end[r]) of device request and delay arrays into its
+    [2, epochs] cells by the epoch of each record's own timer (2^shift cycles from t0; the
+    first and the last epoch are catch-alls), bit for bit what delay_series gives; `total`
+    is merged on the device.  Pointers are plain integers (tensor.data_ptr()).
+    Needs a GPU: there is no host fallback."""
+    _prefix = "pu_dseries"
+
+    def __init__(self, count: int, epochs: int, t0: int = 0, shift: int = 0, device: int = 0):
+        self._n, self._e = count, epochs
+        self._open(count, epochs, t0, shift, device)
+
+    @property
+    def epochs(self) -> int:
+        """Epochs of a replica's series."""
+        return int(lib().pu_dseries_epochs(self._handle()))
+
+    def read(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Cells of replicas [first, first + n): A.DSERIES_DTYPE [n, 2, epochs] (waits for the set's calls)."""
+        n = self._count(first, n)
+        out = np.zeros((max(n, 0), 2, self._e), dtype=A.DSERIES_DTYPE)
+        self._call("read", first, n, _as(out, A.DseriesCell))
+        return out
+
+    def total(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """The cells merged over replicas [first, first + n): A.DSERIES_DTYPE [2, epochs]; count,
+        sum and nonpos add, max is the largest, so ranks merge what this returns the same way."""
+        out = np.zeros((2, self._e), dtype=A.DSERIES_DTYPE)
+        self._call("read_total", first, self._count(first, n), _as(out, A.DseriesCell))
+        return out

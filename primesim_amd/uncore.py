@@ -17,8 +17,9 @@ library, its signature table and the rules for calling it), `engine`, `streams`,
 """
 from ._abi import PU_REPLAY_CLOSED, PU_REPLAY_OPEN, PU_REQ_FMT_16, PU_REQ_FMT_32  # noqa: F401
 from ._native import LIB_PATH, PU_ERRORS, UncoreError, last_error, lib, library_source_hash  # noqa: F401
-from .delays import (DeviceDelayHistogram, DeviceDelaySummary, DeviceDelayTail, delay_histogram, delay_tail,  # noqa: F401
-                     dhist_bucket_bounds, dhist_bucket_of, histogram_quantiles, summarize_delays)
+from .delays import (DeviceDelayHistogram, DeviceDelaySeries, DeviceDelaySummary, DeviceDelayTail,  # noqa: F401
+                     delay_histogram, delay_series, delay_tail, dhist_bucket_bounds, dhist_bucket_of, dseries_epoch_of,
+                     histogram_quantiles, summarize_delays)
 from .engine import (InsMem, UncoreManager, config_from_dict, load_config, parse_config, unit_network,  # noqa: F401
                      unit_queue)
 from .msglog import (MSG_BARRIER, MSG_MEM_REQUESTS, MSG_NEW_THREAD, MSG_PROCESS_FINISHING,  # noqa: F401

@@ -32,9 +32,17 @@ histogram's; 64 K + 16 B per replica): every replica's "read" and "write" object
 (position: the request's place among the replica's measured requests), and one last line
 carries the K slowest of the whole ensemble with the "replica" of each.
 
+With --series E:SHIFT[:T0] the delays are kept over simulated time on the device as well
+(DeviceDelaySeries.add on the same stream, after the other stages' adds; 64 E bytes per
+replica): epochs of 2^SHIFT cycles of the requests' own timers from T0 (default 0) on, the
+first and the last of the E epochs catching everything before and after.  Every replica's
+"read" and "write" objects gain "series": {"count": [...], "sum": [...], "max": [...],
+"nonpos": [...]}, E entries each (nonpos: the delays <= 0; the mean of an epoch is sum /
+count), and one last line carries the same for the cells merged over the replicas.
+
 With --warmup-chunks K the cold start is simulated once: replica 0 alone runs K chunks of
 stream 0 (the other replicas get empty ranges; nothing goes to the summaries,
-histograms or lists of the slowest), then every other replica becomes a copy of it (UncoreManager.fork_replica)
+histograms, lists of the slowest or series), then every other replica becomes a copy of it (UncoreManager.fork_replica)
 and every other stream continues from stream 0's position with its own seed
 (DeviceStreamSet.fork), all on the same stream, and the --chunks measured chunks run as
 usual.  The forks share their warm-up: they are correlated until their own streams have
@@ -140,6 +148,18 @@ def tail_total_line(replicas: int, entries, reps, counts) -> dict:
             "slowest": {name: slowest_list(entries[c], counts[c], reps[c]) for c, name in enumerate(("read", "write"))}}
 
 
+def series_object(cells) -> dict:
+    """One class's epoch series (A.DSERIES_DTYPE cells, one per epoch) as the "series" object."""
+    return {f: [int(v) for v in cells[f]] for f in ("count", "sum", "max", "nonpos")}
+
+
+def series_total_line(replicas: int, epochs: int, shift: int, t0: int, cells) -> dict:
+    """The last line of --series: the cells merged over the replicas (DeviceDelaySeries.total), per class."""
+    return {"replicas": replicas,
+            "series": {"epochs": epochs, "shift": shift, "t0": t0,
+                       **{name: series_object(cells[c]) for c, name in enumerate(("read", "write"))}}}
+
+
 def link_entry(cfg, q: int, visits: int, block_visits=None) -> dict:
     """Queue q of the configuration with its ends (pu_config_queue_ends) and its visit count."""
     import primesim_amd as P
@@ -194,6 +214,8 @@ def main() -> int:
                     help="also keep a log-linear delay histogram on the device and print p50 / p90 / p99 / p99.9")
     ap.add_argument("--tail", type=int, default=0, metavar="K",
                     help="also keep every replica's K slowest reads and writes on the device (1 .. 64)")
+    ap.add_argument("--series", metavar="E:SHIFT[:T0]",
+                    help="also keep the delays per epoch of 2^SHIFT cycles from T0 on the device (E of 1 .. 512 epochs)")
     ap.add_argument("--warmup-chunks", type=int, default=0,
                     help="warm replica 0 alone for this many chunks, then fork it and its stream to the others")
     args = ap.parse_args()
@@ -201,6 +223,16 @@ def main() -> int:
         ap.error("--placement-seed and --skew-max go with --msglog")
     if not 0 <= args.tail <= 64:
         ap.error("--tail takes a list length of 1 .. 64")
+    series = None
+    if args.series:
+        try:
+            series = [int(v) for v in args.series.split(":")]
+        except ValueError:
+            series = []
+        if len(series) == 2:
+            series.append(0)
+        if len(series) != 3 or not 1 <= series[0] <= 512 or not 0 <= series[1] <= 62 or not -(1 << 63) <= series[2] < 1 << 63:
+            ap.error("--series takes E:SHIFT[:T0], E of 1 .. 512 epochs of 2^SHIFT cycles (SHIFT of 0 .. 62) from T0")
 
     import numpy as np
     import torch
@@ -250,7 +282,8 @@ def main() -> int:
     dres = P.DeviceRunResults(um) if args.results else None
     dhist = P.DeviceDelayHistogram(R) if args.quantiles else None
     dtail = P.DeviceDelayTail(R, args.tail) if args.tail else None
-    records = totals = qbuckets = total = tails = tail_total = None
+    dseries = P.DeviceDelaySeries(R, series[0], t0=series[2], shift=series[1]) if series else None
+    records = totals = qbuckets = total = tails = tail_total = cells = cells_total = None
     nlinks = 0
     try:
         if not args.msglog:
@@ -276,6 +309,9 @@ def main() -> int:
             if dtail is not None:
                 dtail.add(d_reqs.data_ptr(), d_del.data_ptr(), d_off.data_ptr(), d_off.data_ptr() + 8, fmt=fmt,
                           stream_ptr=sp)
+            if dseries is not None:
+                dseries.add(d_reqs.data_ptr(), d_del.data_ptr(), d_off.data_ptr(), d_off.data_ptr() + 8, fmt=fmt,
+                            stream_ptr=sp)
         if dres is not None:
             dres.gather(stream_ptr=sp)                                  # one launch, after the last chunk
         summaries = dsum.read()                                         # waits for the last add
@@ -289,6 +325,9 @@ def main() -> int:
         if dtail is not None:
             tails = dtail.read()                                        # waits for the last add
             tail_total = dtail.total()
+        if dseries is not None:
+            cells = dseries.read()                                      # waits for the last add
+            cells_total = dseries.total()
         stream.synchronize()
         served = dss.position() if args.msglog else int(dss.positions().min())
         if served != n * (args.chunks + args.warmup_chunks):
@@ -302,6 +341,8 @@ def main() -> int:
             dhist.close()
         if dtail is not None:
             dtail.close()
+        if dseries is not None:
+            dseries.close()
         dsum.close()
         dss.close()
         um.close()
@@ -315,6 +356,9 @@ def main() -> int:
         if tails is not None:
             for c, name in enumerate(("read", "write")):
                 line[name]["slowest"] = slowest_list(tails[0][r][c], tails[1][r][c])
+        if cells is not None:
+            for c, name in enumerate(("read", "write")):
+                line[name]["series"] = series_object(cells[r][c])
         if records is not None:
             line["results"] = results_object(cfg, records[r])
         print(json.dumps(line))
@@ -324,6 +368,8 @@ def main() -> int:
         print(json.dumps(total_line(R, total[0], total[1])))
     if tail_total is not None:
         print(json.dumps(tail_total_line(R, *tail_total)))
+    if cells_total is not None:
+        print(json.dumps(series_total_line(R, series[0], series[1], series[2], cells_total)))
     return 0
 
 
